@@ -9,13 +9,19 @@ resident in HBM, random-init weights.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Every rank exits with code 2 when WORLD_SIZE differs from --gpus.
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed
+step returned (logits, loss, trans_loss) as DIR/<name>.npy, rank 0's; the inputs and the initial weights come from fixed
+seeds, so two builds can be compared output for output.  With --full the line also carries
   roofline      : the dominant hand-written kernel of the step (by summed time over its launches in one step),
                   timed live with HIP events on the launch stream, vs the gfx950 peak that bounds it;
   kernels       : the same measurement for every hot-path kernel family (incl. the plain CDF-quantise
                   kernel on a 2^26-element tensor, the "quant-kernel HBM GB/s" of BASELINE.json);
   cpu_baseline  : the eager-torch CPU restatement of the reference (oracle/torch_ref.py, kind "port") timed on
-                  this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                  the host cores on a bounded sample of the same workload (rank 0, N=1 only);
+  dp_selftest, other_configs : the data-parallel form of the step at world size 1 and BASELINE.json's other
+                  configurations (N=1 only).
+The --no-* options below switch single parts of --full off.
 """
 import argparse
 import json
@@ -50,6 +56,10 @@ def parse():
                     help="learning rate (default: the reference's 0.04 for the CIFAR nets; 0.004 for resnet50_dann, whose "
                          "reference default 0.04 assumes ImageNet-pretrained weights (dann_office/model/resnet.py:274-288, no "
                          "network here): from RANDOM init 0.04 diverges within ~20 steps, in the eager-torch restatement too)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the per-kernel roofline measurements, the "
+                    "CPU baseline, the data-parallel probe and BASELINE.json's other configurations (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits, loss, trans_loss) as DIR/<name>.npy (float32)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernels", action="store_true", help="skip the per-kernel roofline measurements")
@@ -906,6 +916,19 @@ def timed_steps(step, x, y, steps, world, dist, dev, sync=None):
     return elapsed, out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each returned value of the last timed step as out_dir/<name>.npy in float32 (a loss the step returns
+    as a plain number is stored as a 0-d array; a missing one, None, is left out).  The logits are [batch, classes]: far
+    below the 64 MB a dump may hold, so they are written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def headline(a, elapsed, images_per_step, world, office, final_ce, final_tl):
     """The driver's JSON line (before the roofline / cpu_baseline / extras are attached): `value` is the WHOLE-JOB aggregate -
     every rank processed steps x images_per_step images in the max-over-ranks time - `scaling` weak (fixed per-GPU batch)."""
@@ -1084,11 +1107,13 @@ def main():
     elapsed, out = timed_steps(step, x, y, a.steps, world, dist, dev)
     logits, ce, tl = out
     assert torch.isfinite(ce).item(), "training step produced a non-finite loss"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"logits": logits, "loss": ce, "trans_loss": tl})
 
     if rank == 0:
         res = headline(a, elapsed, images_per_step, world, office, float(ce.detach()),
                        float(tl.detach()) if tl is not None else None)
-        if not a.no_kernels and not office:
+        if a.full and not a.no_kernels and not office:
             counts = {}
             units = [3, 3, 3] if a.model == "resnet20" else [9, 9, 9]
             # site F per stage: 16x32x32, 32x16x16, 64x8x8 ; stem + 2/block + 1 skip in the first block of stages 2,3
@@ -1099,7 +1124,7 @@ def main():
                                             folded=not a.no_fuse_bn, nhwc=not a.nchw, shapes=not a.no_shapes)
             res["roofline"] = roof
             res["kernels"] = kernels
-        if world == 1 and not a.no_cpu_baseline and not office:
+        if a.full and world == 1 and not a.no_cpu_baseline and not office:
             res["cpu_baseline"] = cpu_baseline(a.batch, a.bits, a.model, a.cpu_steps)
             res["speedup_vs_cpu_baseline"] = res["value"] / res["cpu_baseline"]["value"]
             if a.model == "resnet20" and not a.no_other_configs:
@@ -1109,11 +1134,11 @@ def main():
                 res["cpu_baseline_cdf_only"] = cpu_baseline(a.batch, a.bits, a.model, a.cpu_steps, tree="cdf",
                                                             thread_counts=(max(8, best // 2), best, best * 2))
 
-        if world == 1 and not office and not a.dp_selftest and not a.no_dp_probe:
+        if a.full and world == 1 and not office and not a.dp_selftest and not a.no_dp_probe:
             # the data-parallel path at world size 1 (RCCL all-reduce of the flat gradient + D bucket between two HIP graphs):
             # what one rank of the N > 1 runs executes per step, minus the wire time (no 8-GPU node in this session)
             res["dp_selftest"] = dp_probe(dev, a)
-        if world == 1 and not office and not a.no_other_configs and a.model == "resnet20" and a.bits == 8:
+        if a.full and world == 1 and not office and not a.no_other_configs and a.model == "resnet20" and a.bits == 8:
             res["other_configs"] = other_configs(dev, a)
             off_dp = res.get("dp_selftest", {}).get("office", {})
             if "ms_per_step" in off_dp and "resnet50_dann_8w8a_b28" in res["other_configs"]:

@@ -148,3 +148,33 @@ def test_gpus_2_dry_run_through_the_self_launch():
     assert res["n_gpus"] == 2 and res["steps"] == 5 and res["config"]["parallelism"] == "dp2" and res["metric"].startswith("dry run")
     assert res["ms_per_step"] >= 2.0                                # rank 1 sleeps 2 ms per step: the slowest rank's clock
     assert res["value"] == 5 * 128 * 2 / (res["ms_per_step"] * 5e-3) or abs(res["value"] * res["ms_per_step"] * 5e-3 - 1280) < 1e-6
+
+
+# ---- a plain run measures the headline only; --full adds the extra measurements, --dump-outputs writes the last step's outputs
+def test_full_and_dump_outputs_are_opt_in():
+    import bench
+    a = _args(gpus=1, steps=5, warmup=1)
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 1
+    argv, sys.argv = sys.argv, ["bench.py", "--steps", "5", "--full", "--dump-outputs", "out"]
+    try:
+        a = bench.parse()
+    finally:
+        sys.argv = argv
+    assert a.full is True and a.dump_outputs == "out"
+    assert not (a.no_kernels or a.no_cpu_baseline or a.no_dp_probe or a.no_other_configs)   # --full runs every extra by default
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    import numpy as np
+    import bench
+    logits = torch.randn(4, 10, generator=torch.Generator().manual_seed(0))
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), {"logits": logits, "loss": torch.tensor(1.5, dtype=torch.float64), "trans_loss": None})
+    assert sorted(os.listdir(d)) == ["logits.npy", "loss.npy"]      # a missing output (None) is left out
+    got = np.load(d / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logits.numpy())
+    loss = np.load(d / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 1.5
+    bench.dump_outputs(str(d), {"trans_loss": 0.0})                 # a loss the step returns as a plain number
+    tl = np.load(d / "trans_loss.npy")
+    assert tl.dtype == np.float32 and tl.shape == () and float(tl) == 0.0

@@ -36,7 +36,7 @@ head, data = rows[0], rows[1:]
 ours = [r for r in data if is_ours(r[0])]
 others = [r for r in data if not is_ours(r[0])]
 with open(os.path.join(out, "kernel_stats_train_step.csv"), "w") as fo:
-    fo.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-shapes --no-dp-probe --no-other-configs   (MI355X)\n")
+    fo.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-shapes --no-dp-probe --no-other-configs   (MI355X)\n")
     fo.write("# 3 eager warm-ups + HIP-graph capture + 33 replays of the ResNet-20 8W/8A CDF+ADMM step (batch 128), then bench.py's per-kernel\n")
     fo.write("# measurement loops (site kernels x ~55 launches per shape, act_quant / copy / add x 23 launches on 2^26 elements)\n")
     fo.write("# --- this repository's kernels (all of them), by total time ---\n")
