@@ -594,6 +594,29 @@ static inline bool bn_shape_ok(int B, int64_t F, int C, int HW, int nhwc) {
   return HW >= 64 && (HW % 64) == 0;                                             // one channel per 64-feature tile
 }
 
+// One site of the folded forward, validated, as the launcher takes it (single, filler and twin launches alike).
+static int site_bn_fold(const alignq_site_bn_args& a, BnFold* out) {
+  if (!a.z || !a.ab || !a.save || !a.ws || !a.stats) return ALIGNQ_EINVAL;
+  if (bad_k(a.k)) return ALIGNQ_EINVAL;
+  if (!bn_shape_ok(a.B, a.F, a.C, a.HW, a.nhwc)) return ALIGNQ_EUNSUPPORTED;
+  BnFold bn = no_bn();
+  bn.ab = a.ab; bn.save = a.save; bn.HW = a.HW; bn.C = a.C; bn.nhwc = a.nhwc;
+  bn.part = (const double*)a.bn_part; bn.gamma = a.bn_gamma; bn.beta = a.bn_beta;
+  bn.running_mean = a.running_mean; bn.running_var = a.running_var; bn.nbt = (long long*)a.num_batches_tracked;
+  bn.momentum = a.momentum; bn.bn_eps = a.bn_eps; bn.relu = a.relu; bn.res = a.residual;
+  if (a.bins_out) {                // N2: the stored activation's level index in alignq_bin_bytes(k, act_range, ADMM) bytes
+    bn.bins = a.bins_out;
+    bn.bin_bytes = alignq_bin_bytes(a.k, a.act_range, ALIGNQ_FORMULA_ADMM);
+    if (bn.bin_bytes == 0 || a.residual) return ALIGNQ_EINVAL;
+  }
+  if (a.conv_parts > 0) {          // bn_part holds the producing convolution's per-workgroup float partials
+    if (!a.nhwc || !a.bn_part) return ALIGNQ_EINVAL;
+    bn.n_parts = a.conv_parts; bn.part_f32 = 1;
+  }
+  *out = bn;
+  return 0;
+}
+
 int alignq_site_partials_bn(const float* z, const void* bn_part, const float* bn_gamma, const float* bn_beta,
                             float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum,
                             float bn_eps, float* ab, float* save, int C, int HW, int B, int64_t F, int k, float act_range,
@@ -615,68 +638,43 @@ int alignq_site_partials_bn_fill(const float* z, const void* bn_part, const floa
                                  float* const* fill_D, const float* const* fill_alterD, const float* const* fill_gamma,
                                  float* const* fill_scal, const int64_t* fill_F, int fill_dim, float fill_mu, float fill_rho,
                                  void* stream) {
-  if (!z || !ab || !save || !ws) return ALIGNQ_EINVAL;
+  const alignq_site_bn_args a{z, bn_part, bn_gamma, bn_beta, running_mean, running_var, num_batches_tracked, momentum, bn_eps, ab,
+                              save, C, HW, B, F, k, act_range, eps, relu, residual, nhwc, conv_parts, xq, bins_out, stats, ws};
   if (n_fill < 0 || n_fill > site_fill_slots(B, F)) return ALIGNQ_EINVAL;
   if (n_fill && (!fill_ws || !fill_D || !fill_alterD || !fill_gamma || !fill_scal || !fill_F || fill_dim < B)) return ALIGNQ_EINVAL;
   const SiteFillArgs fa{n_fill, fill_ws, fill_D, fill_alterD, fill_gamma, fill_scal, fill_F, fill_dim, fill_mu, fill_rho};
-  if (bad_k(k)) return ALIGNQ_EINVAL;
-  if (!bn_shape_ok(B, F, C, HW, nhwc)) return ALIGNQ_EUNSUPPORTED;
-  BnFold bn = no_bn();
-  bn.ab = ab; bn.save = save; bn.HW = HW; bn.C = C; bn.nhwc = nhwc;
-  bn.part = (const double*)bn_part; bn.gamma = bn_gamma; bn.beta = bn_beta;
-  bn.running_mean = running_mean; bn.running_var = running_var; bn.nbt = (long long*)num_batches_tracked;
-  bn.momentum = momentum; bn.bn_eps = bn_eps; bn.relu = relu; bn.res = residual;
-  if (bins_out) {                  // N2: the stored activation's level index in alignq_bin_bytes(k, act_range, ADMM) bytes
-    bn.bins = bins_out;
-    bn.bin_bytes = alignq_bin_bytes(k, act_range, ALIGNQ_FORMULA_ADMM);
-    if (bn.bin_bytes == 0 || residual) return ALIGNQ_EINVAL;
-  }
-  if (conv_parts > 0) {          // bn_part holds the producing convolution's per-workgroup float partials
-    if (!nhwc || !bn_part) return ALIGNQ_EINVAL;
-    bn.n_parts = conv_parts; bn.part_f32 = 1;
-  }
+  BnFold bn;
+  if (int rc = site_bn_fold(a, &bn)) return rc;
   return launch_partials4(true, geom(B, F), z, B, F, k, act_range, eps, xq, stats, (float*)ws, (hipStream_t)stream, bn,
                           n_fill ? &fa : nullptr);
 }
 
 // Two sites of one shape in one launch (include/alignq.h): each described as alignq_site_partials_bn's arguments.
-static int site_bn_fold(const alignq_site_bn_args& a, BnFold* out) {
-  if (!a.z || !a.ab || !a.save || !a.ws || !a.stats) return ALIGNQ_EINVAL;
-  if (bad_k(a.k)) return ALIGNQ_EINVAL;
-  if (!bn_shape_ok(a.B, a.F, a.C, a.HW, a.nhwc)) return ALIGNQ_EUNSUPPORTED;
-  BnFold bn = no_bn();
-  bn.ab = a.ab; bn.save = a.save; bn.HW = a.HW; bn.C = a.C; bn.nhwc = a.nhwc;
-  bn.part = (const double*)a.bn_part; bn.gamma = a.bn_gamma; bn.beta = a.bn_beta;
-  bn.running_mean = a.running_mean; bn.running_var = a.running_var; bn.nbt = (long long*)a.num_batches_tracked;
-  bn.momentum = a.momentum; bn.bn_eps = a.bn_eps; bn.relu = a.relu; bn.res = a.residual;
-  if (a.bins_out) {
-    bn.bins = a.bins_out;
-    bn.bin_bytes = alignq_bin_bytes(a.k, a.act_range, ALIGNQ_FORMULA_ADMM);
-    if (bn.bin_bytes == 0 || a.residual) return ALIGNQ_EINVAL;
-  }
-  if (a.conv_parts > 0) {
-    if (!a.nhwc || !a.bn_part) return ALIGNQ_EINVAL;
-    bn.n_parts = a.conv_parts; bn.part_f32 = 1;
-  }
-  *out = bn;
-  return 0;
-}
-
 int alignq_site_partials_bn_twin(const alignq_site_bn_args* a, const alignq_site_bn_args* b, void* stream) {
   if (!a || !b) return ALIGNQ_EINVAL;
   if (a->B != b->B || a->F != b->F || a->k != b->k || a->act_range != b->act_range || a->eps != b->eps) return ALIGNQ_EUNSUPPORTED;
   if (a->ws == b->ws || a->stats == b->stats || (a->xq && a->xq == b->xq) || a->ab == b->ab) return ALIGNQ_EINVAL;   // two sites, two sets of buffers
   BnFold bna, bnb;
-  int rc = site_bn_fold(*a, &bna);
-  if (rc) return rc;
-  rc = site_bn_fold(*b, &bnb);
-  if (rc) return rc;
+  if (int rc = site_bn_fold(*a, &bna)) return rc;
+  if (int rc = site_bn_fold(*b, &bnb)) return rc;
   return launch_partials4_twin(geom(a->B, a->F), a->B, a->F, a->k, a->act_range, a->eps, a->z, a->xq, a->stats, (float*)a->ws, bna,
                                b->z, b->xq, b->stats, (float*)b->ws, bnb, (hipStream_t)stream);
 }
 
 size_t alignq_site_bn_part_bytes(int64_t F, int nhwc) {
   return (nhwc ? (size_t)F : (size_t)((F + 31) / 32)) * 2 * sizeof(float);   // <= per column | per smallest backward tile
+}
+
+// One site of the folded backward, validated, as the launcher takes it (single, filler and twin launches alike).
+static int site_bwd_bn_fold(const alignq_site_bwd_bn_args& q, BnFold* out) {
+  if (!q.S || !q.z || !q.ab || !q.save || !q.stats || !q.dx || !q.dx_part) return ALIGNQ_EINVAL;
+  if (q.y_bins && (q.y_relu || (q.y_bin_bytes != 1 && q.y_bin_bytes != 2))) return ALIGNQ_EINVAL;
+  if (!bn_shape_ok(q.B, q.F, q.C, q.HW, q.nhwc)) return ALIGNQ_EUNSUPPORTED;
+  BnFold bn = no_bn();
+  bn.ab = q.ab; bn.save = q.save; bn.HW = q.HW; bn.C = q.C; bn.nhwc = q.nhwc;
+  bn.dx_part = q.dx_part; bn.y = q.y_relu; bn.dres = q.dresidual; bn.ybins = q.y_bins; bn.bin_bytes = q.y_bin_bytes;
+  *out = bn;
+  return 0;
 }
 
 int alignq_site_bwd_apply_bn(const float* g, const float* S, const float* z, const float* ab, const float* save, int C,
@@ -694,7 +692,8 @@ int alignq_site_bwd_apply_bn_fill(const float* g, const float* S, const float* z
                                   float* dresidual, const float* stats, int B, int64_t F, float act_range, float eps,
                                   float* dx, float* dx_part, int n_fill, const void* const* fill_ws, float* const* fill_dw,
                                   const int* fill_n_slabs, const int* fill_n_elem, void* stream) {
-  if (!S || !z || !ab || !save || !stats || !dx || !dx_part) return ALIGNQ_EINVAL;
+  const alignq_site_bwd_bn_args q{g, S, z, ab, save, C, HW, nhwc, y_relu, y_bins, y_bin_bytes, dresidual, stats, B, F, act_range,
+                                  eps, dx, dx_part};
   if (n_fill < 0 || n_fill > alignq_site_bwd_fill_slots(B, F)) return ALIGNQ_EINVAL;
   if (n_fill && (!fill_ws || !fill_dw || !fill_n_slabs || !fill_n_elem)) return ALIGNQ_EINVAL;
   alignq_wgr::RedFill fill{};
@@ -705,11 +704,8 @@ int alignq_site_bwd_apply_bn_fill(const float* g, const float* S, const float* z
     fill.blk0[i + 1] = fill.blk0[i] + alignq_wgr::wgrad_reduce_blocks(fill_n_slabs[i], fill_n_elem[i], 256);
   }
   for (int i = n_fill; i < alignq_wgr::kFill; i++) fill.blk0[i + 1] = fill.blk0[i];
-  if (y_bins && (y_relu || (y_bin_bytes != 1 && y_bin_bytes != 2))) return ALIGNQ_EINVAL;
-  if (!bn_shape_ok(B, F, C, HW, nhwc)) return ALIGNQ_EUNSUPPORTED;
-  BnFold bn = no_bn();
-  bn.ab = ab; bn.save = save; bn.HW = HW; bn.C = C; bn.nhwc = nhwc;
-  bn.dx_part = dx_part; bn.y = y_relu; bn.dres = dresidual; bn.ybins = y_bins; bn.bin_bytes = y_bin_bytes;
+  BnFold bn;
+  if (int rc = site_bwd_bn_fold(q, &bn)) return rc;
   return launch_bwd4(true, geom(B, F), g, S, z, stats, B, F, act_range, eps, dx, (hipStream_t)stream, bn, n_fill ? &fill : nullptr);
 }
 
@@ -717,20 +713,12 @@ int alignq_site_bwd_apply_bn_fill(const float* g, const float* S, const float* z
 int alignq_site_bwd_apply_bn_twin(const alignq_site_bwd_bn_args* a, const alignq_site_bwd_bn_args* b, void* stream) {
   if (!a || !b) return ALIGNQ_EINVAL;
   if (a->B != b->B || a->F != b->F || a->act_range != b->act_range || a->eps != b->eps) return ALIGNQ_EUNSUPPORTED;
-  BnFold bn[2];
-  const alignq_site_bwd_bn_args* two[2] = {a, b};
-  for (int i = 0; i < 2; i++) {
-    const alignq_site_bwd_bn_args& q = *two[i];
-    if (!q.S || !q.z || !q.ab || !q.save || !q.stats || !q.dx || !q.dx_part) return ALIGNQ_EINVAL;
-    if (q.y_bins && (q.y_relu || (q.y_bin_bytes != 1 && q.y_bin_bytes != 2))) return ALIGNQ_EINVAL;
-    if (!bn_shape_ok(q.B, q.F, q.C, q.HW, q.nhwc)) return ALIGNQ_EUNSUPPORTED;
-    bn[i] = no_bn();
-    bn[i].ab = q.ab; bn[i].save = q.save; bn[i].HW = q.HW; bn[i].C = q.C; bn[i].nhwc = q.nhwc;
-    bn[i].dx_part = q.dx_part; bn[i].y = q.y_relu; bn[i].dres = q.dresidual; bn[i].ybins = q.y_bins; bn[i].bin_bytes = q.y_bin_bytes;
-  }
+  BnFold bna, bnb;
+  if (int rc = site_bwd_bn_fold(*a, &bna)) return rc;
+  if (int rc = site_bwd_bn_fold(*b, &bnb)) return rc;
   if (a->dx == b->dx || a->dx_part == b->dx_part) return ALIGNQ_EINVAL;
-  return launch_bwd4_twin(a->B, a->F, a->act_range, a->eps, a->g, a->S, a->z, a->stats, a->dx, bn[0], b->g, b->S, b->z, b->stats, b->dx,
-                          bn[1], (hipStream_t)stream);
+  return launch_bwd4_twin(a->B, a->F, a->act_range, a->eps, a->g, a->S, a->z, a->stats, a->dx, bna, b->g, b->S, b->z, b->stats, b->dx,
+                          bnb, (hipStream_t)stream);
 }
 
 int alignq_site_prep_fused(const float* D, const float* alterD, const float* gamma, int dim, const float* scal, float mu,

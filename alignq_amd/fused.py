@@ -393,16 +393,79 @@ class _TwinState(threading.local):
 _twin = _TwinState()
 
 
+class _ParkedPair:
+    """Where two site launches of a twin pair meet: the first parks its arguments (and the tensors they point at), the second
+    launches both with `two(a, b, st)`; where that returns ALIGNQ_EUNSUPPORTED (another shape, or a site that fills the chip alone)
+    or the two came on different streams, `one(args, st)` launches them one after the other.  flush() launches a parked site on
+    its own.  tracked: a parked site is listed for flush_bwd_twins() (the backward's pairs)."""
+
+    def __init__(self, one, two, name, tracked=False):
+        self.one, self.two, self.name, self.tracked = one, two, name, tracked
+        self.pending = None
+
+    def _unpark(self):
+        p, self.pending = self.pending, None
+        if self.tracked and self in _bwd_twins.open:
+            _bwd_twins.open.remove(self)
+        return p
+
+    def flush(self):
+        if self.pending is not None:
+            args, _keep, st = self._unpark()
+            self.one(args, st)
+
+    def add(self, args, keep, st):
+        if self.pending is None:
+            self.pending = (args, keep, st)
+            if self.tracked:
+                _bwd_twins.open.append(self)
+            return
+        pa, _pk, pst = self._unpark()
+        rc = self.two(ctypes.byref(pa), ctypes.byref(args), st) if pst == st else L.EUNSUPPORTED
+        if rc == L.EUNSUPPORTED:
+            self.one(pa, pst)
+            self.one(args, st)
+        else:
+            L.check(rc, self.name)
+
+
+def _site_fwd_launch(a, st, fill=(), dim=0, mu=0.0, rho=0.0):
+    """alignq_site_partials_bn_fill for the site `a` (L.SiteBnArgs); fill: DeferredLosses.take_fill's items (dim / mu / rho theirs)."""
+    nf = len(fill)
+    L.check(L.load().alignq_site_partials_bn_fill(
+        a.z, a.bn_part, a.bn_gamma, a.bn_beta, a.running_mean, a.running_var, a.num_batches_tracked, a.momentum, a.bn_eps, a.ab,
+        a.save, a.C, a.HW, a.B, a.F, a.k, a.act_range, a.eps, a.relu, a.residual, a.nhwc, a.conv_parts, a.xq, a.bins_out, a.stats,
+        a.ws, nf, L.ptr_array([r.ws for r in fill]) if nf else None, L.ptr_array([r.D for r in fill]) if nf else None,
+        L.ptr_array([r.A for r in fill]) if nf else None, L.ptr_array([r.Gm for r in fill]) if nf else None,
+        L.ptr_array([r.scal for r in fill]) if nf else None, L.i64_array([r.F for r in fill]) if nf else None, dim, float(mu),
+        float(rho), st), "alignq_site_partials_bn_fill")
+
+
+def _site_bwd_launch(a, st, fill=()):
+    """alignq_site_bwd_apply_bn_fill for the site `a` (L.SiteBwdBnArgs); fill: DeferredWgrads.take_site's items."""
+    nf = len(fill)
+    L.check(L.load().alignq_site_bwd_apply_bn_fill(
+        a.g, a.S, a.z, a.ab, a.save, a.C, a.HW, a.nhwc, a.y_relu, a.y_bins, a.y_bin_bytes, a.dresidual, a.stats, a.B, a.F,
+        a.act_range, a.eps, a.dx, a.dx_part, nf, L.ptr_array([f[0] for f in fill]) if nf else None,
+        L.ptr_array([f[1] for f in fill]) if nf else None, (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
+        (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None, st), "alignq_site_bwd_apply_bn_fill")
+
+
 class twin_sites:
     """Inside this context two BN-folded ADMM sites of ONE shape whose single launches leave half the chip idle (F <= 8192 at batch
     128) are launched TOGETHER (alignq_site_partials_bn_twin): the sites behind a transition block's two convolutions, model/
     resnet.py PreActBlock_conv_Q.forward - one node of the step's chain instead of two, bit-identical results.  The first site's
     forward parks its arguments, the second launches both; a site without a partner (or of another shape) is launched on its own,
-    at the latest when the context ends.  Only the whole-model deferred step (fused.DeferredLosses) uses it."""
+    at the latest when the context ends.  Only the whole-model deferred step (fused.DeferredLosses) uses it.
+    bwd: where the pair's backward launches meet (carried by both sites' autograd contexts; alignq_site_bwd_apply_bn_twin).  The only
+    reader of what that launch writes - the producing convolution's backward - calls flush_bwd_twins() before it takes the lazy
+    records, so a site whose partner never ran is launched on its own there; DeferredWgrads flushes as well when the backward ends."""
 
     def __init__(self):
-        self.pending = None
-        self.bwd = _BwdTwin()
+        self.fwd = _ParkedPair(_site_fwd_launch, lambda a, b, st: L.load().alignq_site_partials_bn_twin(a, b, st),
+                               "alignq_site_partials_bn_twin")
+        self.bwd = _ParkedPair(_site_bwd_launch, lambda a, b, st: L.load().alignq_site_bwd_apply_bn_twin(a, b, st),
+                               "alignq_site_bwd_apply_bn_twin", tracked=True)
 
     def __enter__(self):
         self.prev, _twin.ctx = _twin.ctx, self
@@ -411,86 +474,9 @@ class twin_sites:
     def __exit__(self, *exc):
         _twin.ctx = self.prev
         if exc[0] is None:
-            self.flush()
-        self.pending = None
+            self.fwd.flush()
+        self.fwd.pending = None
         return False
-
-    @staticmethod
-    def _single(args, st):
-        a = args
-        L.check(L.load().alignq_site_partials_bn(a.z, a.bn_part, a.bn_gamma, a.bn_beta, a.running_mean, a.running_var,
-                                                 a.num_batches_tracked, a.momentum, a.bn_eps, a.ab, a.save, a.C, a.HW, a.B, a.F, a.k,
-                                                 a.act_range, a.eps, a.relu, a.residual, a.nhwc, a.conv_parts, a.xq, a.bins_out,
-                                                 a.stats, a.ws, st), "alignq_site_partials_bn")
-
-    def flush(self):
-        if self.pending is not None:
-            args, _keep, st = self.pending
-            self.pending = None
-            self._single(args, st)
-
-    def add(self, args, keep, st):
-        if self.pending is None:
-            self.pending = (args, keep, st)
-            return
-        pa, _pk, pst = self.pending
-        self.pending = None
-        rc = L.load().alignq_site_partials_bn_twin(ctypes.byref(pa), ctypes.byref(args), st) if pst == st else L.EUNSUPPORTED
-        if rc == L.EUNSUPPORTED:           # another shape, or a site that fills the chip alone: one after the other
-            self._single(pa, pst)
-            self._single(args, st)
-        else:
-            L.check(rc, "alignq_site_partials_bn_twin")
-
-
-def _site_bwd_launch(lib, g_y, S, z, ab, save, C, HW, nhwc, y, ybins, dres, stats, B, F, act_range, eps, dx, part, fill, st):
-    nf = len(fill)
-    L.check(lib.alignq_site_bwd_apply_bn_fill(
-        L.ptr(g_y), L.ptr(S), L.ptr(z), L.ptr(ab), L.ptr(save), C, HW, nhwc, L.ptr(y), L.ptr(ybins),
-        ybins.element_size() if ybins is not None else 0, L.ptr(dres) if y is not None else None, L.ptr(stats), B, F,
-        act_range, eps, L.ptr(dx), L.ptr(part), nf, L.ptr_array([f[0] for f in fill]) if nf else None,
-        L.ptr_array([f[1] for f in fill]) if nf else None, (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
-        (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None, st), "alignq_site_bwd_apply_bn_fill")
-
-
-class _BwdTwin:
-    """Where the backward launches of a twin pair meet (created by `twin_sites`, carried by both sites' autograd contexts): the first
-    site's backward parks its arguments, the second launches both (alignq_site_bwd_apply_bn_twin).  The only reader of what the
-    launch writes - the producing convolution's backward - calls flush_bwd_twins() before it takes the lazy records, so a site whose
-    partner never ran is launched on its own there; DeferredWgrads flushes as well when the backward ends."""
-
-    def __init__(self):
-        self.pending = None
-
-    @staticmethod
-    def _single(a, st):
-        L.check(L.load().alignq_site_bwd_apply_bn(a.g, a.S, a.z, a.ab, a.save, a.C, a.HW, a.nhwc, a.y_relu, a.y_bins, a.y_bin_bytes,
-                                                  a.dresidual, a.stats, a.B, a.F, a.act_range, a.eps, a.dx, a.dx_part, st),
-                "alignq_site_bwd_apply_bn")
-
-    def flush(self):
-        if self.pending is not None:
-            args, _keep, st = self.pending
-            self.pending = None
-            if self in _bwd_twins.open:
-                _bwd_twins.open.remove(self)
-            self._single(args, st)
-
-    def add(self, args, keep, st):
-        if self.pending is None:
-            self.pending = (args, keep, st)
-            _bwd_twins.open.append(self)
-            return
-        pa, _pk, pst = self.pending
-        self.pending = None
-        if self in _bwd_twins.open:
-            _bwd_twins.open.remove(self)
-        rc = L.load().alignq_site_bwd_apply_bn_twin(ctypes.byref(pa), ctypes.byref(args), st) if pst == st else L.EUNSUPPORTED
-        if rc == L.EUNSUPPORTED:
-            self._single(pa, pst)
-            self._single(args, st)
-        else:
-            L.check(rc, "alignq_site_bwd_apply_bn_twin")
 
 
 class _BwdTwins(threading.local):
@@ -502,8 +488,8 @@ _bwd_twins = _BwdTwins()
 
 
 def flush_bwd_twins():
-    """Launch every parked site backward of this thread (see _BwdTwin) - called by whoever is about to read or to launch a reader of
-    a site backward's outputs."""
+    """Launch every parked site backward of this thread (see twin_sites.bwd) - called by whoever is about to read or to launch a
+    reader of a site backward's outputs."""
     for t in list(_bwd_twins.open):
         t.flush()
 
@@ -565,31 +551,23 @@ class BNSiteFn(torch.autograd.Function):
         stats = torch.empty(4, F, dtype=torch.float32, device=dev)
         scal = rec.scal if rec is not None else torch.empty(4, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.alignq_site_ws_bytes(B, F), dtype=torch.uint8, device=dev)
+        args = L.SiteBnArgs(L.ptr(z), L.ptr(ws_bn), L.ptr(bn_weight), L.ptr(bn_bias), L.ptr(running_mean), L.ptr(running_var),
+                            L.ptr(nbt), float(momentum), float(bn_eps), L.ptr(ab), L.ptr(save), C, HW, B, F, int(k), float(act_range),
+                            float(eps), int(bool(relu)), L.ptr(res), int(nhwc), int(conv_parts), L.ptr(y), L.ptr(bins), L.ptr(stats),
+                            L.ptr(ws))
         tw = _twin.ctx
         if (tw is not None and rec is not None and _active is not None and nhwc and res is None
                 and lib.alignq_site_fill_slots(B, F) > 0):
             # twin launch (round 6): inside `twin_sites()` two half-chip sites of one shape share ONE launch - the first only parks its
             # arguments (its outputs are allocated; nobody reads them before the partner's forward launches both), no filler role
-            args = L.SiteBnArgs(L.ptr(z), L.ptr(ws_bn), L.ptr(bn_weight), L.ptr(bn_bias), L.ptr(running_mean), L.ptr(running_var),
-                                L.ptr(nbt), float(momentum), float(bn_eps), L.ptr(ab), L.ptr(save), C, HW, B, F, int(k),
-                                float(act_range), float(eps), int(bool(relu)), None, int(nhwc), int(conv_parts), L.ptr(y), L.ptr(bins),
-                                L.ptr(stats), L.ptr(ws))
-            tw.add(args, (z, ws_bn, bn_weight, bn_bias, running_mean, running_var, nbt, ab, save, y, bins, stats, ws), st)
+            tw.fwd.add(args, (z, ws_bn, bn_weight, bn_bias, running_mean, running_var, nbt, ab, save, y, bins, stats, ws), st)
             ctx.twin_bwd = tw.bwd           # the pair's backward launches meet there again (BNSiteFn.backward)
         else:
             if tw is not None:
-                tw.flush()         # (keep the launches in program order: a parked site goes first)
+                tw.fwd.flush()     # (keep the launches in program order: a parked site goes first)
             # filler role: earlier sites' slab reductions ride in this launch when it leaves CUs idle (DeferredLosses.take_fill)
             fill = _active.take_fill(rec, B, F, dim, mu, rho) if (rec is not None and _active is not None) else []
-            nf = len(fill)
-            L.check(lib.alignq_site_partials_bn_fill(
-                L.ptr(z), L.ptr(ws_bn), L.ptr(bn_weight), L.ptr(bn_bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt),
-                float(momentum), float(bn_eps), L.ptr(ab), L.ptr(save), C, HW, B, F, int(k), float(act_range), float(eps),
-                int(bool(relu)), L.ptr(res), int(nhwc), int(conv_parts), L.ptr(y), L.ptr(bins), L.ptr(stats), L.ptr(ws), nf,
-                L.ptr_array([r.ws for r in fill]) if nf else None, L.ptr_array([r.D for r in fill]) if nf else None,
-                L.ptr_array([r.A for r in fill]) if nf else None, L.ptr_array([r.Gm for r in fill]) if nf else None,
-                L.ptr_array([r.scal for r in fill]) if nf else None, L.i64_array([r.F for r in fill]) if nf else None,
-                dim, float(mu), float(rho), st), "alignq_site_partials_bn_fill")
+            _site_fwd_launch(args, st, fill, dim, mu, rho)
         if rec is not None:      # reduced with all other sites in DeferredLosses.total()
             rec.ws, rec.D, rec.A, rec.Gm, rec.B, rec.F, rec.dim = ws, D, A, Gm, B, F, dim
             rec.mu, rec.rho = float(mu), float(rho)
@@ -642,18 +620,17 @@ class BNSiteFn(torch.autograd.Function):
             dres = torch.empty_like(z) if y is not None else g_y
         fresh = all(p is None or p.grad is None for p in ctx.bn_params)
         lazy2 = ctx.from_qconv == 2 and active_wgrads() is not None and active_wgrads().fresh_grads and fresh
+        args = L.SiteBwdBnArgs(L.ptr(g_y), L.ptr(S), L.ptr(z), L.ptr(ab), L.ptr(save), C, HW, nhwc, L.ptr(y), L.ptr(ybins),
+                               ybins.element_size() if ybins is not None else 0, L.ptr(dres) if y is not None else None, L.ptr(stats),
+                               B, F, act_range, eps, L.ptr(dx), L.ptr(part))
         if ctx.twin_bwd is not None and lazy2 and g_y is not None:
             # the backward of a twin pair (round 6): nothing else is launched by this node on the lazy path, and the one consumer of dx
             # and of the per-tile sums - the producing convolution's backward - flushes the pair before it reads them (take_lazy_dz)
-            args = L.SiteBwdBnArgs(L.ptr(g_y), L.ptr(S), L.ptr(z), L.ptr(ab), L.ptr(save), C, HW, nhwc, L.ptr(y), L.ptr(ybins),
-                                   ybins.element_size() if ybins is not None else 0, L.ptr(dres) if y is not None else None,
-                                   L.ptr(stats), B, F, act_range, eps, L.ptr(dx), L.ptr(part))
             ctx.twin_bwd.add(args, (g_y, S, z, ab, save, y, ybins, dres, stats, dx, part), st)
         else:
             flush_bwd_twins()
             # filler role: the narrow sites' launches take pending filter-gradient slab reductions along (DeferredWgrads.take_site)
-            fill = active_wgrads().take_site(B, F) if active_wgrads() is not None else []
-            _site_bwd_launch(lib, g_y, S, z, ab, save, C, HW, nhwc, y, ybins, dres, stats, B, F, act_range, eps, dx, part, fill, st)
+            _site_bwd_launch(args, st, active_wgrads().take_site(B, F) if active_wgrads() is not None else [])
         dgam = torch.empty(C, dtype=torch.float32, device=dev) if has_w else None
         dbet = torch.empty(C, dtype=torch.float32, device=dev) if has_b else None
         # the in-kernel form fills dgam / dbet AFTER autograd has adopted them as .grad: only valid while both .grad are
