@@ -17,6 +17,8 @@ args = SimpleNamespace(
     gpus=[0],
     global_corr=None,       # not a reference option: True / a process group -> exact-global-batch corr
     pack_bins=False,        # not a reference option: plain quantiser nodes keep int8/int16 bins for backward
+    param=0.3,              # options_office.py (DSAN tree): weight of the LMMD term
+    bottle_neck=True,       # options_office.py (DSAN tree): store_true with default True, i.e. always on
 )
 
 

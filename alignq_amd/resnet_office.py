@@ -234,3 +234,62 @@ class DANN(nn.Module):
 
 def resnet50_dann(wbit, abit, stage="aligned", **kwargs):
     return DANN(resnet50_quant, wbit, abit, stage)
+
+
+class DSAN(nn.Module):
+    """cdf_alignment_admm/dsan_office/model/resnet.py:355-382: the ResNet feature extractor, the bottleneck `bottle`
+    (Linear(2048, 256), args.bottle_neck) and the classifier `cls_fc`, trained with the LMMD loss (alignq_amd.mmd).
+    One deviation from the ADMM tree: the LMMD compares the BOTTLENECKED source and target features, as the CDF-only tree does
+    (cdf_alignment/dsan_office/model/resnet.py:346-358).  The ADMM tree passes the 2048-wide `self.target` beside the 256-wide
+    source (resnet.py:378), which fails in torch.cat on the first training iteration (DSAN).  The features and
+    predictions are not kept as attributes (main.py never reads them; they would pin the iteration's autograd graph)."""
+
+    def __init__(self, arch, wbit, abit, stage, num_classes=31):
+        super().__init__()
+        self.feature_layers = arch(wbit, abit, stage)
+        self.bottle_neck = bool(config.args.bottle_neck)
+        if self.bottle_neck:
+            self.bottle = nn.Linear(2048, 256)
+            self.cls_fc = nn.Linear(256, num_classes)
+        else:
+            self.cls_fc = nn.Linear(2048, num_classes)
+
+    def _head(self, feature):
+        return self.bottle(feature) if self.bottle_neck else feature
+
+    def forward(self, source, target, s_label):
+        """(source class logits, LMMD + trans losses of both passes / train_batch_size^2); in eval mode no target pass and
+        an LMMD of 0, as in the reference."""
+        from . import mmd
+        src, trans_loss = self.feature_layers(source)
+        src = self._head(src)
+        s_pred = self.cls_fc(src)
+        if self.training:
+            tgt, tgt_trans_loss = self.feature_layers(target)
+            tgt = self._head(tgt)
+            p = torch.softmax(self.cls_fc(tgt).detach(), dim=1)
+            loss = mmd.lmmd(src, tgt, s_label, p)
+            trans_loss = trans_loss + tgt_trans_loss
+        else:
+            loss = 0
+        return s_pred, loss + trans_loss / (config.args.train_batch_size ** 2)
+
+    def forward_dual(self, x_src, x_tgt, s_label):
+        """forward() of a training iteration as ONE traversal (like DANN.forward_dual): both batches back to back through the
+        per-sample convolutions (batch statistics, sites, correlations per domain in pass order; ADMM.D: the target's), one
+        `bottle` and one `cls_fc` GEMM over the 2B rows, and the LMMD over the two halves of the bottleneck output in place."""
+        from . import mmd
+        B = x_src.shape[0]
+        x = torch.cat([x_src, x_tgt], 0)
+        if x_src.dim() == 4 and x_src.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        feature, trans_loss = self.feature_layers(x, groups=2)
+        h = self._head(feature.view(-1, 2048))
+        logits = self.cls_fc(h)
+        p = torch.softmax(logits[B:].detach(), dim=1)
+        loss = mmd.lmmd_pair(h, s_label, p)
+        return logits[:B], loss + trans_loss / (config.args.train_batch_size ** 2)
+
+
+def resnet50_dsan(wbit, abit, stage="aligned", **kwargs):
+    return DSAN(resnet50_quant, wbit, abit, stage)

@@ -391,16 +391,13 @@ class OfficeTrainStep:
         self.model, self.alpha = model, alpha
         named = list(model.named_parameters())
         self.param_admm = [(n, p) for n, p in named if "alterD" in n or "gamma" in n]
-        self.optimizer_t = SGD([{"params": list(model.feature.parameters())},
-                                {"params": list(model.class_classifier.parameters()), "lr": lr},
-                                {"params": list(model.domain_classifier.parameters()), "lr": lr}],
-                               lr=lr / 10, momentum=momentum, weight_decay=weight_decay)
+        self.optimizer_t = SGD(self._param_groups(lr), lr=lr / 10, momentum=momentum, weight_decay=weight_decay)
         self.optimizer_admm = ADMM_OPT([p for _, p in self.param_admm])
         # main.py:405-410 (param_t there lists ALL named parameters, so j indexes feature.parameters())
         self.idx = [j for j, (n, _) in enumerate(named) if ("conv" in n or "downsample.0" in n) and "weight" in n][1:]
         self.alterD_idx = [j for j, (n, _) in enumerate(self.param_admm) if "alterD" in n]
         self.gamma_idx = [j for j, (n, _) in enumerate(self.param_admm) if "gamma" in n]
-        f = model.feature
+        f = self._backbone()
         self.blocks = [b for layer in (f.layer1, f.layer2, f.layer3, f.layer4) for b in layer]
         self.convs = []
         for b in self.blocks:
@@ -414,13 +411,24 @@ class OfficeTrainStep:
         self._graph2: Optional[torch.cuda.CUDAGraph] = None
         self._static = None
 
+    def _backbone(self):
+        """The ResNet feature extractor (DANN: `feature`)."""
+        return self.model.feature
+
+    def _param_groups(self, rate):
+        """main.py:324-328: the feature extractor at the optimizer's default learning rate (rate / 10), the heads at `rate`."""
+        m = self.model
+        return [{"params": list(m.feature.parameters())},
+                {"params": list(m.class_classifier.parameters()), "lr": rate},
+                {"params": list(m.domain_classifier.parameters()), "lr": rate}]
+
     def stage_weights(self, on=True):
         """Quantise the conv weights per ResNet stage, each stage right before its forward (ResNet.forward calls back), instead of
         all of them before the first layer.  Same per-tensor arithmetic (the multi-tensor kernels treat every filter alone), 5 x 2
         launches each way instead of 2.  For data parallelism: a stage's weight gradients then leave the weight quantiser's
         backward when the backward passes that stage, so their buckets' all-reduces overlap the earlier stages' backward
         (dp.attach_office switches it on)."""
-        f = self.model.feature
+        f = self._backbone()
         if on:
             layers = (f.layer1, f.layer2, f.layer3, f.layer4)
             owner = {id(m): i + 1 for i, layer in enumerate(layers) for m in layer.modules() if hasattr(m, "quantize_fn")}
@@ -490,11 +498,7 @@ class OfficeTrainStep:
         with LEARNING_RATE = lr / (1 + 10 (epoch-1) / num_epochs)^0.75 for the two heads and a tenth of it for the feature
         extractor.  A captured step is re-captured (graph kernel arguments hold the learning rates)."""
         rate = lr / (1.0 + 10.0 * (epoch - 1) / num_epochs) ** 0.75
-        m = self.model
-        self.optimizer_t = SGD([{"params": list(m.feature.parameters())},
-                                {"params": list(m.class_classifier.parameters()), "lr": rate},
-                                {"params": list(m.domain_classifier.parameters()), "lr": rate}],
-                               lr=rate / 10, momentum=momentum, weight_decay=weight_decay)
+        self.optimizer_t = SGD(self._param_groups(rate), lr=rate / 10, momentum=momentum, weight_decay=weight_decay)
         if self._graph is not None:
             # the first step of the epoch creates the fresh momentum buffers (buf = grad) and must not be the captured one
             self._graph, self._recapture = None, True
@@ -586,3 +590,75 @@ class OfficeTrainStep:
         self._graph = graph
         self._static = (sxs, sys_, sxt, _detached(outs))
         return self
+
+
+def dsan_lambd(num_iters, num_epochs, num_iterations):
+    """cdf_alignment_admm/dsan_office/main.py:381-382: the LMMD ramp for global iteration `num_iters` (= num_iterations *
+    epoch + i) of a run of `num_epochs` epochs with `num_iterations` iterations each."""
+    import numpy as np
+    p = float(num_iters) / num_epochs / num_iterations
+    return 2. / (1. + np.exp(-10 * p) + 1e-6) - 1
+
+
+class DSANTrainStep(OfficeTrainStep):
+    """One DSAN iteration of the Office tree (cdf_alignment_admm/dsan_office/main.py:386-478): zero_grad x2 -> DSAN forward
+    (source pass, target pass, LMMD over the bottlenecked features: resnet_office.DSAN) -> CE(s_pred, y_s) + param * lambd *
+    loss_mmd -> backward -> SGD.step(idx, w_cdf, w_pdf, lam, lam2) over feature_layers (lr / 10), bottle and cls_fc (lr) ->
+    ADMM_OPT.step with each ADMM.D holding the target pass's D.  new_epoch re-creates the SGD as main.py:316-329 does.
+    `param * lambd` lives in a device scalar that __call__ fills before the step runs, so one captured graph serves every
+    iteration of the ramp.  Not covered: data parallelism, src_only_flag."""
+
+    def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=5e-4, channels_last=False, fuse_relu=True, fuse_bn=True,
+                 dual=None, qconv=True, pack_bins=True):
+        super().__init__(model, lr=lr, momentum=momentum, weight_decay=weight_decay, channels_last=channels_last,
+                         fuse_relu=fuse_relu, fuse_bn=fuse_bn, dual=dual, qconv=qconv, pack_bins=pack_bins)
+        dev = next(self.model.parameters()).device
+        self._coef = torch.zeros(1, dtype=torch.float32, device=dev)     # args.param * lambd of the coming iteration
+
+    def _backbone(self):
+        return self.model.feature_layers
+
+    def _param_groups(self, rate):
+        """main.py:318-322"""
+        m = self.model
+        heads = ([{"params": list(m.bottle.parameters()), "lr": rate}] if m.bottle_neck else []) + \
+            [{"params": list(m.cls_fc.parameters()), "lr": rate}]
+        return [{"params": list(m.feature_layers.parameters())}] + heads
+
+    def set_lambd(self, lambd):
+        """Stage args.param * lambd (main.py:407, formed in Python floats as there) for the next iteration: one fill, no sync."""
+        self._coef.fill_(float(config.args.param * lambd))
+
+    def _forward_backward(self, xs, ys, xt, set_to_none=True, overlap=False):
+        m = self.model
+        self.optimizer_t.zero_grad(set_to_none=set_to_none)
+        self.optimizer_admm.zero_grad(set_to_none=set_to_none)
+        if self.channels_last:
+            xs = xs.contiguous(memory_format=torch.channels_last)
+            xt = xt.contiguous(memory_format=torch.channels_last)
+        if not self._staged:
+            prequantize_weights(self.all_convs, pack=self.qconv)
+        if self.dual and xs.shape == xt.shape:
+            s_pred, loss_mmd = m.forward_dual(xs, xt, ys)
+        else:
+            # (the target pass quantises the weights itself: the parked ones are taken by the source pass)
+            s_pred, loss_mmd = m(xs, xt, ys)
+        loss = F.cross_entropy(s_pred, ys) + self._coef * loss_mmd
+        if self._wgrads is not None:
+            with self._wgrads as wg:
+                loss.backward()
+                wg.flush()
+        else:
+            loss.backward()
+        return s_pred, loss, loss_mmd
+
+    def __call__(self, xs, ys, xt, lambd):
+        """(s_pred, loss, loss_mmd) of the iteration; lambd: dsan_lambd(...) of this iteration."""
+        self.set_lambd(lambd)
+        return super().__call__(xs, ys, xt)
+
+    def capture(self, xs, ys, xt, warmup=2, lambd=None):
+        """OfficeTrainStep.capture; the warm-up iterations use `lambd` if given, else the last staged value."""
+        if lambd is not None:
+            self.set_lambd(lambd)
+        return super().capture(xs, ys, xt, warmup=warmup)

@@ -687,6 +687,25 @@ int alignq_bnq_bwd(const float* g, const float* z, const float* y, const void* m
                    int C, int groups, float act_range, int relu, float* dz, float* dres, float* dgamma, float* dbeta, void* ws,
                    void* stream);
 
+/* ---- DSAN's LMMD loss (cdf_alignment_admm/dsan_office/utils/mmd.py:9-41 and utils/Weight.py:10-54; the CDF tree's copies are
+ * identical apart from the device).  Replaces the reference's per-iteration device -> host round trip (Weight.cal_weight builds
+ * the B x B class weights in NumPy) with three launches and no synchronisation.  X = [x_src; x_tgt] (n = 2B rows of D floats;
+ * two pointers, so the halves of one [2B][D] tensor need no concatenation), s_label: [B] int64 source labels, p_tgt: [B][C]
+ * target class probabilities (no gradient flows to either).  kernel_mul > 0, fix_sigma <= 0 means the data bandwidth
+ * sum(L2) / (n^2 - n) (mmd.py:15-19).  Class weights as NumPy forms them (fp64, cast to fp32); a source label outside [0, C)
+ * belongs to no class (it adds to no count and to no weight).  loss: [1], 0 when no class is common to the source labels and
+ * the target argmax, or when the kernel matrix holds a NaN (mmd.py:33-35); the backward then writes exact zeros.
+ * Supported: 2 <= B <= 64, any D, C <= 64, kernel_num <= 8 (else ALIGNQ_EUNSUPPORTED).  Fixed reduction orders, no atomics:
+ * bit-reproducible.  ws: alignq_lmmd_ws_bytes(B, D) bytes (0 = unsupported shape); the forward leaves in it what the backward
+ * reads, so a backward uses the workspace of ITS forward.                                                                      */
+size_t alignq_lmmd_ws_bytes(int B, int64_t D);
+int alignq_lmmd_fwd(const float* x_src, const float* x_tgt, const int64_t* s_label, const float* p_tgt, int B, int64_t D,
+                    int C, double kernel_mul, int kernel_num, double fix_sigma, float* loss, void* ws, void* stream);
+/* backward of alignq_lmmd_fwd: dx_src / dx_tgt [B][D] = g * d loss / d x, with g the upstream gradient read from DEVICE memory
+ * (g[0]), so a captured step serves any loss scale.  x_src / x_tgt: the forward's inputs, unchanged.                        */
+int alignq_lmmd_bwd(const float* g, const float* x_src, const float* x_tgt, const void* ws, int B, int64_t D, float* dx_src,
+                    float* dx_tgt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
