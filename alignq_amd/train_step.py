@@ -74,7 +74,162 @@ def _detached(outs):
     return tuple(t.detach() if torch.is_tensor(t) else t for t in outs)
 
 
-class TrainStep:
+class _CapturedStep:
+    """The HIP-graph lifecycle every training step shares: static input buffers, the warm-up and the capture into one graph (or
+    two around the eager data-parallel all-reduce), replay, the eager fallback for an off-shape batch and re-capture.  A
+    subclass builds `model`, `channels_last`, `optimizer_t`, `optimizer_admm`, `admms` and `_wgrads`, calls `_init_capture` from
+    its __init__ and supplies `_forward_backward(*inputs, set_to_none, overlap)` (overlap=True: an eager iteration, which runs
+    the grad_hook itself) and `_optimizer_steps()`."""
+
+    def _init_capture(self, grad_hook):
+        self.grad_hook = grad_hook          # e.g. the data-parallel all-reduce (alignq_amd.dp)
+        self._graph: Optional[torch.cuda.CUDAGraph] = None
+        self._graph2: Optional[torch.cuda.CUDAGraph] = None
+        self._static = None                 # the input buffers the graphs read
+        self._outs = None                   # the captured iteration's results
+        self._recapture = False             # capture from the next eager call's inputs (new_epoch)
+
+    def _iteration(self, *inputs, set_to_none=True):
+        outs = self._forward_backward(*inputs, set_to_none=set_to_none, overlap=True)
+        self._optimizer_steps()
+        return _detached(outs)
+
+    def _backward(self, roots, grads=None, set_to_none=True):
+        """All filter-gradient slab reductions of the backward in one launch behind it (fused.DeferredWgrads).  A
+        DeferredWgrads(fresh_grads=True) promises that every .grad is None when the backward starts: only after set_to_none."""
+        wg = self._wgrads
+        if wg is not None and (set_to_none or not wg.fresh_grads):
+            with wg:
+                torch.autograd.backward(roots, grads)
+                wg.flush()
+        else:
+            torch.autograd.backward(roots, grads)
+
+    def __call__(self, *inputs):
+        if self._graph is None:
+            outs = self._iteration(*inputs)
+            if self._recapture:
+                self._recapture = False
+                self.capture(*inputs, warmup=0)
+            return outs
+        if any(x.shape != s.shape for x, s in zip(inputs, self._static)):
+            # off-shape batch (the reference's loaders have no drop_last: CIFAR's last batch is 80 of 128): a captured
+            # graph only fits its static shapes, so this one iteration runs eagerly
+            return self._eager_fallback(*inputs)
+        # a loader that writes its batches straight into `static_inputs()` (the target of its host-to-device copy) hands the
+        # same tensors back: nothing to stage
+        for x, s in zip(inputs, self._static):
+            if x is not s:
+                s.copy_(x, non_blocking=True)
+        self._graph.replay()
+        if self._graph2 is not None:
+            # data-parallel: only the collectives run eagerly between the two captured halves (the buckets are packed in the
+            # first graph and unpacked at the start of the second)
+            self.grad_hook.reduce()
+            self._graph2.replay()
+        return self._outs
+
+    def static_inputs(self):
+        """The buffers the captured graph reads ((x, y) or (xs, ys, xt); images in the step's memory format).  Fill them in
+        place — e.g. as the destination of the loader's host-to-device copy — and call the step with these very tensors: the
+        per-step staging copies (a layout-converting one for NCHW input) are skipped.  None before `capture`."""
+        return self._static
+
+    def _eager_fallback(self, *inputs):
+        """The graph's own gradient / D tensors (which p.grad and ADMM.D name between replays) are put back afterwards."""
+        opts = [o for o in (self.optimizer_t, self.optimizer_admm) if o is not None]
+        params = list({id(p): p for o in opts for g in o.param_groups for p in g["params"]}.values())
+        keep_g, keep_D = [p.grad for p in params], [m.D for m in self.admms]
+        # a data-parallel hook rebinds its flat bucket to the off-shape layout during this iteration; the graphs keep packing
+        # into / unpacking from the bucket that was current at capture, so the eager reduce() between them must see that one
+        # again afterwards (otherwise it all-reduces the stale short-batch buffer and the replicas diverge silently)
+        hook = self.grad_hook
+        keep_hook = hook.snapshot() if hasattr(hook, "snapshot") else None
+        try:
+            return self._iteration(*inputs)
+        finally:
+            for p, g in zip(params, keep_g):
+                p.grad = g
+            for m, D in zip(self.admms, keep_D):
+                m.D = D
+            if hasattr(hook, "restore"):
+                hook.restore(keep_hook)
+
+    def _assert_momentum_buffers(self, who):
+        """A momentum buffer created INSIDE a capture is baked into the graph with first=1 (buf = grad on every replay:
+        silently momentum-free training) and lives in the graph's private pool.  Capture therefore needs every parameter the
+        step updates to own its buffer already, i.e. at least one eager step since the optimizer was created."""
+        opt = self.optimizer_t
+        momentum = [p for g in opt.param_groups if g["momentum"] != 0 for p in g["params"]]
+        if momentum and (all(p.grad is None for g in opt.param_groups for p in g["params"])
+                         or any(p.grad is not None and "momentum_buffer" not in opt.state[p] for p in momentum)):
+            raise RuntimeError(f"{who}: a parameter has no momentum buffer yet; run at least one eager iteration "
+                               "(capture(..., warmup>=1)) before capturing the step")
+
+    def _capture(self, inputs, warmup):
+        who = f"{type(self).__name__}.capture"
+        release_step_graphs(self.admms)
+        assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], who)
+        static = tuple(t.clone(memory_format=torch.channels_last) if (self.channels_last and t.dim() == 4) else t.clone()
+                       for t in inputs)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._iteration(*static, set_to_none=False)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._assert_momentum_buffers(who)
+        release_step_graphs(self.admms)          # (an unfused site of the warm-up keeps D with its graph)
+        # inside the capture grads are re-created (set_to_none=True): no zero-fill and no accumulate-add per
+        # parameter; the fresh grad tensors live in the graph's private pool at fixed addresses and stay
+        # referenced by p.grad, so the captured optimizer kernels (and the eager all-reduce) see them on replay.
+        self.optimizer_t.zero_grad(set_to_none=True)
+        if self.optimizer_admm is not None:
+            self.optimizer_admm.zero_grad(set_to_none=True)
+        hook = self.grad_hook
+        split = hook is not None and hook.active()
+        # An initialised process group matters even WITHOUT a hook: its watchdog thread polls HIP events of earlier collectives,
+        # which the default (global) capture mode forbids while ANY stream captures; under capture_error_mode="thread_local" HIP
+        # calls of other threads neither fail nor invalidate the capture.
+        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+        cap_mode = dict(capture_error_mode="thread_local") if dist_on else {}
+        if split:
+            # The warm-up iterations issued collectives: a barrier orders every rank behind its peers' warm-up collectives and the
+            # device synchronise retires them, so none is in flight when the capture starts.  Only on the all-ranks data-parallel
+            # path: a step without an active hook (after dp.detach, a rank-local evaluation step) must not meet its peers here.
+            torch.distributed.barrier()
+            torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        self._graph2 = None
+        if not split:
+            with torch.cuda.graph(graph, **cap_mode):
+                outs = self._iteration(*static, set_to_none=True)
+        else:
+            # data parallel: forward + backward (+ the buckets packed) | eager all-reduces | bucket unpack + optimizer steps
+            # overlapped (dp.BucketedGradAllReduce): the hooks pack each bucket and publish its flag where the captured backward
+            # completes it; reduce() then starts bucket i's all-reduce beside the rest of the replayed backward.  Phased
+            # (dp.GradAndDAllReduce): every bucket is packed behind the backward.
+            overlapped = hasattr(hook, "capture_begin")
+            with torch.cuda.graph(graph, **cap_mode):
+                if overlapped:
+                    hook.capture_begin()
+                outs = self._forward_backward(*static, set_to_none=True, overlap=False)
+                if overlapped:
+                    hook.capture_end()
+                else:
+                    hook.pack()
+            graph2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph2, pool=graph.pool(), **cap_mode):
+                hook.unpack()
+                self._optimizer_steps()
+            self._graph2 = graph2
+        self._graph = graph
+        self._static, self._outs = static, _detached(outs)
+        return self
+
+
+class TrainStep(_CapturedStep):
     def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=1e-4, grad_hook=None, defer_losses=True, fuse_bn=True,
                  channels_last=False, qconv=True, pack_bins=True):
         """channels_last: keep activations and conv weights in torch.channels_last memory (values, parameter names and
@@ -121,14 +276,11 @@ class TrainStep:
                 self.admms += [layer.admm0, layer.admm1]
                 if layer.skip_conv is not None:
                     self.admms.append(layer.admm_skip)
-        self.grad_hook = grad_hook          # e.g. the data-parallel all-reduce (alignq_amd.dp)
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph2: Optional[torch.cuda.CUDAGraph] = None
-        self._static = None
+        self._init_capture(grad_hook)
         self._one = None
 
     # -------------------------------------------------------------------------------------------
-    def _forward_backward(self, x, y, set_to_none=True):
+    def _forward_backward(self, x, y, set_to_none=True, overlap=False):
         model = self.model
         self.optimizer_t.zero_grad(set_to_none=set_to_none)
         if self.optimizer_admm is not None:
@@ -173,12 +325,9 @@ class TrainStep:
             else [ce, trans_loss]
         if self._one is None or self._one.device != ce.device:
             self._one = torch.ones((), dtype=torch.float32, device=ce.device)
-        if self._wgrads is not None and set_to_none:
-            with self._wgrads as wg:          # all filter-gradient slab reductions in one launch after the backward
-                torch.autograd.backward(roots, [self._one] * len(roots))
-                wg.flush()
-        else:
-            torch.autograd.backward(roots, [self._one] * len(roots))
+        self._backward(roots, [self._one] * len(roots), set_to_none)
+        if overlap and self.grad_hook is not None:
+            self.grad_hook(self)            # the eager iteration's all-reduce, between backward and the optimizer steps
         return logits, ce, trans_loss
 
     def _optimizer_steps(self):
@@ -194,72 +343,6 @@ class TrainStep:
             # CDF-only tree (main.py:308 crashes as shipped): plain momentum SGD, no grad rewrite
             self.optimizer_t.step([], [], [], config.args.lam, config.args.lam2)
 
-    def _iteration(self, x, y, set_to_none=True):
-        outs = self._forward_backward(x, y, set_to_none)
-        if self.grad_hook is not None:
-            self.grad_hook(self)
-        self._optimizer_steps()
-        return _detached(outs)
-
-    def __call__(self, x, y):
-        if self._graph is None:
-            return self._iteration(x, y)
-        sx, sy = self._static[0], self._static[1]
-        if x.shape != sx.shape or y.shape != sy.shape:
-            # off-shape batch (the reference's loaders have no drop_last: CIFAR's last batch is 80 of 128): a captured
-            # graph only fits its static shapes, so this one iteration runs eagerly; the graph's own gradient / D tensors
-            # (which p.grad and ADMM.D name between replays) are put back afterwards
-            return self._eager_fallback(x, y)
-        # a loader that writes its batches straight into `static_inputs()` (the target of its host-to-device copy) hands the
-        # same tensors back: nothing to stage
-        if x is not sx:
-            sx.copy_(x, non_blocking=True)
-        if y is not sy:
-            sy.copy_(y, non_blocking=True)
-        self._graph.replay()
-        if self._graph2 is not None:
-            # data-parallel: only the collective runs eagerly between the two captured halves (pack / unpack of the flat
-            # bucket are captured at the end of the first and the start of the second graph)
-            self.grad_hook.reduce() if hasattr(self.grad_hook, "reduce") else self.grad_hook(self)
-            self._graph2.replay()
-        return self._static[2]
-
-    def static_inputs(self):
-        """(x, y) buffers the captured graph reads (x in the step's memory format).  Fill them in place — e.g. as the
-        destination of the loader's host-to-device copy — and call the step with these very tensors: the per-step staging
-        copies (a layout-converting one for NCHW input) are skipped.  None before `capture`."""
-        return None if self._static is None else (self._static[0], self._static[1])
-
-    def _eager_fallback(self, x, y):
-        params = [p for _, p in self.param_t + self.param_admm]
-        keep_g, keep_D = [p.grad for p in params], [m.D for m in self.admms]
-        # a data-parallel hook rebinds its flat bucket to the off-shape layout during this iteration; the graphs keep packing
-        # into / unpacking from the bucket that was current at capture, so the eager reduce() between them must see that one
-        # again afterwards (otherwise it all-reduces the stale short-batch buffer and the replicas diverge silently)
-        hook = self.grad_hook
-        keep_hook = hook.snapshot() if hasattr(hook, "snapshot") else None
-        try:
-            return self._iteration(x, y)
-        finally:
-            for p, g in zip(params, keep_g):
-                p.grad = g
-            for m, D in zip(self.admms, keep_D):
-                m.D = D
-            if hasattr(hook, "restore"):
-                hook.restore(keep_hook)
-
-    def _assert_momentum_buffers(self):
-        """A momentum buffer created INSIDE a capture is baked into the graph with first=1 (buf = grad on every replay:
-        silently momentum-free training) and lives in the graph's private pool.  Capture therefore needs every parameter the
-        step updates to own its buffer already, i.e. at least one eager step since the optimizer was created."""
-        for group in self.optimizer_t.param_groups:
-            if group["momentum"] == 0:
-                continue
-            for p in group["params"]:
-                if p.requires_grad and "momentum_buffer" not in self.optimizer_t.state[p]:
-                    raise RuntimeError("TrainStep.capture: a parameter has no momentum buffer yet; run at least one eager "
-                                       "iteration (capture(..., warmup>=1)) before capturing the step")
-
     # -------------------------------------------------------------------------------------------
     def set_lr(self, lr):
         """The reference steps a StepLR scheduler once per epoch (main.py:112,150).  Scalar hyper-parameters are baked into
@@ -270,13 +353,13 @@ class TrainStep:
             changed |= g["lr"] != lr
             g["lr"] = lr
         if changed and self._graph is not None:
-            self.capture(self._static[0], self._static[1], warmup=0)
+            self.capture(*self._static, warmup=0)
         return self
 
     def capture(self, x, y, warmup=3):
         """Capture the iteration into HIP graphs.  Runs `warmup` eager iterations first (they DO update
         the model, as real steps) so allocator pools, momentum buffers, pointer tables and MIOpen plans
-        exist.  Without a grad_hook the whole iteration is ONE graph; with one (data parallel) it is two
+        exist.  Without an active grad_hook the whole iteration is ONE graph; with one (data parallel) it is two
         graphs (forward+backward | optimizer steps) with the all-reduce launched eagerly in between."""
         # refusals first: nothing below may touch the model before them (ADVICE r4: the warm-up iterations are real steps)
         if getattr(self, "_global_corr_undo", None) is not None or getattr(config.args, "global_corr", None) is not None:
@@ -291,59 +374,10 @@ class TrainStep:
                                "inside the forward and inside autograd's backward call, where the capture cannot be split, and "
                                "captured collectives need a process group created with TORCH_NCCL_ASYNC_ERROR_HANDLING=0 "
                                "(DESIGN.md section 6) - call the step eagerly")
-        release_step_graphs(self.admms)
-        assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], "TrainStep.capture")
-        sx = x.clone(memory_format=torch.channels_last) if (self.channels_last and x.dim() == 4) else x.clone()
-        sy = y.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._iteration(sx, sy, set_to_none=False)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._assert_momentum_buffers()
-        release_step_graphs(self.admms)          # (an unfused site of the warm-up keeps D with its graph)
-        # An initialised process group matters even WITHOUT a hook: its watchdog thread polls HIP events of earlier collectives,
-        # which the default (global) capture mode forbids while ANY stream captures; under capture_error_mode="thread_local" HIP
-        # calls of other threads neither fail nor invalidate the capture.
-        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-        if dist_on and self.grad_hook is not None:
-            # The warm-up iterations issued collectives: a barrier orders every rank behind its peers' warm-up collectives and the
-            # device synchronise retires them, so none is in flight when the capture starts.  Only on the all-ranks data-parallel
-            # path: a step without a hook (after dp.detach, a rank-local evaluation step) must not meet its peers here.
-            torch.distributed.barrier()
-            torch.cuda.synchronize()
-        cap_mode = dict(capture_error_mode="thread_local") if dist_on else {}
-        graph = torch.cuda.CUDAGraph()
-        self._graph2 = None
-        # inside the capture grads are re-created (set_to_none=True): no zero-fill and no accumulate-add per
-        # parameter; the fresh grad tensors live in the graph's private pool at fixed addresses and stay
-        # referenced by p.grad, so the captured optimizer kernels (and the eager all-reduce) see them on replay.
-        self.optimizer_t.zero_grad(set_to_none=True)
-        if self.optimizer_admm is not None:
-            self.optimizer_admm.zero_grad(set_to_none=True)
-        if self.grad_hook is None:
-            with torch.cuda.graph(graph, **cap_mode):
-                outs = self._iteration(sx, sy, set_to_none=True)
-        else:
-            phased = hasattr(self.grad_hook, "reduce")
-            with torch.cuda.graph(graph, **cap_mode):
-                outs = self._forward_backward(sx, sy, set_to_none=True)
-                if phased:
-                    self.grad_hook.pack()
-            graph2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph2, pool=graph.pool(), **cap_mode):
-                if phased:
-                    self.grad_hook.unpack()
-                self._optimizer_steps()
-            self._graph2 = graph2
-        self._graph = graph
-        self._static = (sx, sy, _detached(outs))
-        return self
+        return self._capture((x, y), warmup)
 
 
-class OfficeTrainStep:
+class OfficeTrainStep(_CapturedStep):
     """One DANN iteration of the Office tree (cdf_alignment_admm/dann_office/main.py:343-456): zero_grad x2 -> source pass
     -> target pass -> src class CE + src/tgt domain CE + both trans losses -> backward -> SGD.step(idx, w_cdf, w_pdf, lam,
     lam2) over the three parameter groups (feature incl. alterD/gamma, class head, domain head: main.py:324-328) ->
@@ -399,17 +433,18 @@ class OfficeTrainStep:
         self.gamma_idx = [j for j, (n, _) in enumerate(self.param_admm) if "gamma" in n]
         f = self._backbone()
         self.blocks = [b for layer in (f.layer1, f.layer2, f.layer3, f.layer4) for b in layer]
+        self.admms = [b.admm0 for b in self.blocks]
         self.convs = []
         for b in self.blocks:
             for k, conv in enumerate((b.conv1, b.conv2, b.conv3, b.downsample)):
                 if conv is not None:
                     self.convs.append(conv[0] if k == 3 else conv)
         self.all_convs = [m for m in model.modules() if hasattr(m, "quantize_fn")]
-        self.grad_hook = grad_hook
         self._staged = False
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph2: Optional[torch.cuda.CUDAGraph] = None
-        self._static = None
+        # the domain labels (main.py:360-361 builds them every iteration) are constants of the batch sizes: kept per
+        # (source batch, target batch, device), so the ones a captured graph reads outlive an off-shape eager iteration
+        self._dom_labels = {}
+        self._init_capture(grad_hook)
 
     def _backbone(self):
         """The ResNet feature extractor (DANN: `feature`)."""
@@ -439,28 +474,40 @@ class OfficeTrainStep:
         self._staged = bool(on)
         return self
 
-    def _iteration(self, xs, ys, xt, set_to_none=True):
-        out = self._forward_backward(xs, ys, xt, set_to_none, overlap=True)
-        self._optimizer_steps()
-        return _detached(out)
-
     def _forward_backward(self, xs, ys, xt, set_to_none=True, overlap=False):
-        m = self.model
+        """The prologue DANN and DSAN share (zero_grad x2, both batches in the step's memory format, the conv weights
+        quantised), then the tree's own forward and loss (`_forward_loss`) and the backward."""
         self.optimizer_t.zero_grad(set_to_none=set_to_none)
         self.optimizer_admm.zero_grad(set_to_none=set_to_none)
-        dev = xs.device
         if self.channels_last:
             xs = xs.contiguous(memory_format=torch.channels_last)
             xt = xt.contiguous(memory_format=torch.channels_last)
-        # the domain labels (main.py:360-361 builds them every iteration) are constants of the batch sizes: kept, not re-filled
-        key = (int(xs.shape[0]), int(xt.shape[0]), dev)
-        if getattr(self, "_dom_labels_key", None) != key:
-            self._dom_labels = (torch.zeros(xs.shape[0], dtype=torch.long, device=dev),
-                                torch.ones(xt.shape[0], dtype=torch.long, device=dev))
-            self._dom_labels_key = key
-        label_src, label_tgt = self._dom_labels
+        labels = self._domain_labels(xs, xt)
         if not self._staged:               # (staged: ResNet.forward quantises each stage's weights right before the stage)
             prequantize_weights(self.all_convs, pack=self.qconv)
+        outs = self._forward_loss(xs, ys, xt, labels)
+        hook = self.grad_hook if overlap else None
+        if hook is not None:
+            hook.begin()              # the buckets' all-reduces start from autograd hooks during this backward
+        # (the weight quantiser's backward finishes the slab reductions before it reads them)
+        self._backward([outs[1]], set_to_none=set_to_none)
+        if hook is not None:
+            hook.finish()
+        return outs
+
+    def _domain_labels(self, xs, xt):
+        """The source / target domain labels (main.py:360-361), created before the weight quantisation: moving their
+        allocation changes where the allocator places the iteration's other buffers, which measurably changes the step time."""
+        key = (int(xs.shape[0]), int(xt.shape[0]), xs.device)
+        if key not in self._dom_labels:
+            self._dom_labels[key] = (torch.zeros(xs.shape[0], dtype=torch.long, device=xs.device),
+                                     torch.ones(xt.shape[0], dtype=torch.long, device=xs.device))
+        return self._dom_labels[key]
+
+    def _forward_loss(self, xs, ys, xt, labels):
+        """(class logits, loss, trans loss) of the DANN iteration."""
+        m = self.model
+        label_src, label_tgt = labels
         if self.dual and xs.shape == xt.shape:
             cls_s, dom_s, dom_t, tl_both = m.forward_dual(xs, xt, alpha=self.alpha)      # (same weights, hence the same W_q,
             tl_s, tl_t = tl_both, 0.0                                                    #  in both of the reference's passes)
@@ -472,24 +519,13 @@ class OfficeTrainStep:
         # (a pass without a loss tensor contributes the NUMBER 0: adding it would be an elementwise launch of its own)
         tl = tl_s if not torch.is_tensor(tl_t) and tl_t == 0 else (tl_t if not torch.is_tensor(tl_s) and tl_s == 0 else tl_s + tl_t)
         loss = F.cross_entropy(cls_s, ys) + F.cross_entropy(dom_s, label_src) + F.cross_entropy(dom_t, label_tgt) + tl
-        hook = self.grad_hook if overlap else None
-        if hook is not None:
-            hook.begin()              # the buckets' all-reduces start from autograd hooks during this backward
-        if self._wgrads is not None:
-            with self._wgrads as wg:  # (the weight quantiser's backward finishes the slab reductions before it reads them)
-                loss.backward()
-                wg.flush()
-        else:
-            loss.backward()
-        if hook is not None:
-            hook.finish()
         return cls_s, loss, tl
 
     def _optimizer_steps(self):
         w_cdf = [c.quantize_fn.weight_cdf for c in self.convs]
         w_pdf = [c.quantize_fn.weight_pdf for c in self.convs]
         self.optimizer_t.step(self.idx, w_cdf, w_pdf, config.args.lam, config.args.lam2)
-        a = [b.admm0 for b in self.blocks]
+        a = self.admms
         self.optimizer_admm.step(self.alterD_idx, self.gamma_idx, [q.D for q in a], [q.alterD for q in a],
                                  [q.gamma for q in a], [q.mu for q in a], [q.rho for q in a])
 
@@ -504,92 +540,9 @@ class OfficeTrainStep:
             self._graph, self._recapture = None, True
         return rate
 
-    def __call__(self, xs, ys, xt):
-        if self._graph is None:
-            out = self._iteration(xs, ys, xt)
-            if getattr(self, "_recapture", False):
-                self._recapture = False
-                self.capture(xs, ys, xt, warmup=0)
-            return out
-        if any(src.shape != dst.shape for dst, src in zip(self._static[:3], (xs, ys, xt))):
-            return self._eager_fallback(xs, ys, xt)       # off-shape (short last) batch: one eager iteration
-        for dst, src in zip(self._static[:3], (xs, ys, xt)):
-            dst.copy_(src, non_blocking=True)
-        self._graph.replay()
-        if self._graph2 is not None:       # data parallel: the buckets' collectives run eagerly between the two graphs
-            self.grad_hook.reduce()
-            self._graph2.replay()
-        return self._static[3]
-
-    def _eager_fallback(self, xs, ys, xt):
-        params = [p for g in self.optimizer_t.param_groups for p in g["params"]]
-        admms = [b.admm0 for b in self.blocks]
-        keep_g, keep_D = [p.grad for p in params], [q.D for q in admms]
-        hook = self.grad_hook
-        keep_hook = hook.snapshot() if hasattr(hook, "snapshot") else None      # see TrainStep._eager_fallback
-        try:
-            return self._iteration(xs, ys, xt)
-        finally:
-            for p, g in zip(params, keep_g):
-                p.grad = g
-            for q, D in zip(admms, keep_D):
-                q.D = D
-            if hasattr(hook, "restore"):
-                hook.restore(keep_hook)
-
     def capture(self, xs, ys, xt, warmup=2):
-        admms = [b.admm0 for b in self.blocks]
-        release_step_graphs(admms)
-        assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], "OfficeTrainStep.capture")
-        fmt = torch.channels_last if self.channels_last else torch.contiguous_format
-        sxs, sys_, sxt = xs.clone(memory_format=fmt), ys.clone(), xt.clone(memory_format=fmt)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._iteration(sxs, sys_, sxt, set_to_none=False)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        for group in self.optimizer_t.param_groups:      # see TrainStep._assert_momentum_buffers
-            for p in group["params"]:
-                if group["momentum"] != 0 and p.grad is not None and "momentum_buffer" not in self.optimizer_t.state[p]:
-                    raise RuntimeError("OfficeTrainStep.capture: a parameter has no momentum buffer yet; run at least one "
-                                       "eager iteration (capture(..., warmup>=1)) before capturing the step")
-        release_step_graphs(admms)
-        self.optimizer_t.zero_grad(set_to_none=True)
-        self.optimizer_admm.zero_grad(set_to_none=True)
-        graph = torch.cuda.CUDAGraph()
-        self._graph2 = None
-        if self.grad_hook is None or not self.grad_hook.active():
-            # (an initialised process group's watchdog thread issues HIP calls of its own: thread-local capture mode, see TrainStep.capture)
-            pg_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-            with torch.cuda.graph(graph, **(dict(capture_error_mode="thread_local") if pg_on else {})):
-                outs = self._iteration(sxs, sys_, sxt, set_to_none=True)
-        else:
-            # data parallel: forward + backward (+ each bucket packed where its last gradient lands) | eager all-reduces, started
-            # per bucket by a flag the replayed graph publishes | bucket unpack + optimizer steps
-            torch.distributed.barrier()
-            torch.cuda.synchronize()
-            mode = dict(capture_error_mode="thread_local")
-            overlapped = hasattr(self.grad_hook, "capture_begin")
-            with torch.cuda.graph(graph, **mode):
-                if overlapped:
-                    # the hooks pack each bucket and publish its flag where the captured backward completes it; reduce() then
-                    # starts bucket i's all-reduce beside the rest of the replayed backward (dp.BucketedGradAllReduce)
-                    self.grad_hook.capture_begin()
-                    outs = self._forward_backward(sxs, sys_, sxt, set_to_none=True, overlap=False)
-                    self.grad_hook.capture_end()
-                else:
-                    outs = self._forward_backward(sxs, sys_, sxt, set_to_none=True, overlap=False)
-                    self.grad_hook.pack()
-            graph2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph2, pool=graph.pool(), **mode):
-                self.grad_hook.unpack()
-                self._optimizer_steps()
-            self._graph2 = graph2
-        self._graph = graph
-        self._static = (sxs, sys_, sxt, _detached(outs))
-        return self
+        """Capture the iteration into HIP graphs after `warmup` eager iterations (TrainStep.capture)."""
+        return self._capture((xs, ys, xt), warmup)
 
 
 def dsan_lambd(num_iters, num_epochs, num_iterations):
@@ -629,28 +582,18 @@ class DSANTrainStep(OfficeTrainStep):
         """Stage args.param * lambd (main.py:407, formed in Python floats as there) for the next iteration: one fill, no sync."""
         self._coef.fill_(float(config.args.param * lambd))
 
-    def _forward_backward(self, xs, ys, xt, set_to_none=True, overlap=False):
+    def _domain_labels(self, xs, xt):
+        return None                        # (no domain classifier)
+
+    def _forward_loss(self, xs, ys, xt, labels):
+        """(source logits, loss, LMMD loss) of the DSAN iteration."""
         m = self.model
-        self.optimizer_t.zero_grad(set_to_none=set_to_none)
-        self.optimizer_admm.zero_grad(set_to_none=set_to_none)
-        if self.channels_last:
-            xs = xs.contiguous(memory_format=torch.channels_last)
-            xt = xt.contiguous(memory_format=torch.channels_last)
-        if not self._staged:
-            prequantize_weights(self.all_convs, pack=self.qconv)
         if self.dual and xs.shape == xt.shape:
             s_pred, loss_mmd = m.forward_dual(xs, xt, ys)
         else:
             # (the target pass quantises the weights itself: the parked ones are taken by the source pass)
             s_pred, loss_mmd = m(xs, xt, ys)
-        loss = F.cross_entropy(s_pred, ys) + self._coef * loss_mmd
-        if self._wgrads is not None:
-            with self._wgrads as wg:
-                loss.backward()
-                wg.flush()
-        else:
-            loss.backward()
-        return s_pred, loss, loss_mmd
+        return s_pred, F.cross_entropy(s_pred, ys) + self._coef * loss_mmd, loss_mmd
 
     def __call__(self, xs, ys, xt, lambd):
         """(s_pred, loss, loss_mmd) of the iteration; lambd: dsan_lambd(...) of this iteration."""

@@ -227,20 +227,39 @@ def _tiny_step(dev, batch=72, **kw):
     return net, TrainStep(net, channels_last=True, qconv=True, **kw)
 
 
-def test_capture_without_momentum_buffers_is_refused(dev):
-    """capture(warmup=0) on a fresh TrainStep would bake first=1 into the graph (buf = grad on every replay)."""
+def _tiny_office_step(dev, batch=6):
+    """OfficeTrainStep on the tiny DANN of fixture G10 (test_office_tiny_dann_two_iterations_vs_reference)."""
+    from alignq_amd import config
+    from alignq_amd.resnet_office import DANN, Bottleneck, ResNet
+    from alignq_amd.train_step import OfficeTrainStep
+    config.args.bitW = config.args.abitW = 4
+    config.args.train_batch_size = config.args.eval_batch_size = batch
+    torch.manual_seed(0)
+    net = DANN(lambda w, a, s: ResNet(w, a, s, Bottleneck, [1, 1, 1, 1], width_per_group=8), 4, 4, "aligned").to(dev).train()
+    return net, OfficeTrainStep(net, lr=0.004, channels_last=True)
+
+
+@pytest.mark.parametrize("tree", ["cifar", "office"])
+def test_capture_without_momentum_buffers_is_refused(dev, tree):
+    """capture(warmup=0) on a fresh step would bake first=1 into the graph (buf = grad on every replay): the CIFAR
+    TrainStep and the Office / DANN OfficeTrainStep alike."""
     from alignq_amd import config
     try:
-        net, step = _tiny_step(dev)
-        x, y = torch.randn(72, 3, 32, 32, device=dev), torch.randint(0, 10, (72,), device=dev)
+        if tree == "cifar":
+            net, step = _tiny_step(dev)
+            inputs = (torch.randn(72, 3, 32, 32, device=dev), torch.randint(0, 10, (72,), device=dev))
+        else:
+            net, step = _tiny_office_step(dev)
+            inputs = (torch.randn(6, 3, 64, 64, device=dev), torch.randint(0, 31, (6,), device=dev),
+                      torch.randn(6, 3, 64, 64, device=dev))
         with pytest.raises(RuntimeError, match="momentum buffer"):
-            step.capture(x, y, warmup=0)
-        step.capture(x, y, warmup=1)                       # one eager step creates them: fine
-        step(x, y)
+            step.capture(*inputs, warmup=0)
+        step.capture(*inputs, warmup=1)                    # one eager step creates them: fine
+        step(*inputs)
         torch.cuda.synchronize()
     finally:
         config.args.bitW = config.args.abitW = 8
-        config.args.train_batch_size = 128
+        config.args.train_batch_size, config.args.eval_batch_size = 128, 100
 
 
 def test_captured_step_runs_an_off_shape_batch_eagerly_and_keeps_its_graph(dev):
