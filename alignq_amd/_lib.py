@@ -187,6 +187,8 @@ SIGNATURES = {
     "alignq_lmmd_ws_bytes": (_sz, [_i, _i64]),
     "alignq_lmmd_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _c.c_double, _i, _c.c_double, _vp, _vp, _vp]),
     "alignq_lmmd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "alignq_bnq_eval_fwd": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "alignq_eval_metrics": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,207 @@
+"""The reference's test() (cdf_alignment_admm/resnet-20-cifar-10/main.py:405-441, dann_office/main.py:502-545; accuracy:
+utils/common.py:78-92) as a step of this repository: eval-mode batch-norm folded into the quantiser (alignq_bnq_eval_fwd, one
+launch per site), the filters quantised once per evaluation instead of once per batch, cross-entropy / Prec@1 / Prec@5
+accumulated on the device (alignq_eval_metrics, one launch per batch, ONE host read per evaluation), the per-batch work
+capturable as one HIP graph.
+
+    ev = EvalStep(model, channels_last=True, qconv=True)
+    with ev:                                  # begin() ... end()
+        ev.capture(x0, y0)                    # optional
+        for x, y in loader:
+            ev(x, y)                          # enqueues; returns the logits; no synchronisation
+        ce, prec1, prec5, n = ev.result()     # the one host read
+
+Differences from the reference's test(): an ADMM site computes no Gram matrices and no ADMM loss and
+leaves ADMM.D alone (test() discards the loss, and the D it stores is overwritten by the next training forward before anything
+reads it); ties are ranked as include/alignq.h states for alignq_eval_metrics.  This holds where alignq_bnq_eval_fwd applies
+(channels-last fp32, C a power of two in [4, 2048], a quantiser of 1..16 bits or none): any other site runs today's `model.eval()`
+composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import fused
+from .train_step import _CapturedStep
+
+_MISSING = object()
+_FLAGS = ("fuse_bn", "fuse_relu", "use_qconv", "emit_bn_stats", "pack_bins", "_wq_stage")
+
+
+class EvalStep(_CapturedStep):
+    """model: resnet.PreActResNet (tree "admm" or "cdf"), resnet_office.DANN (class logits at alpha = 0) or resnet_office.DSAN
+    (s_pred).  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
+    without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
+    end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
+
+    def __init__(self, model, channels_last=True, qconv=True, pack_bins=True):
+        if channels_last:
+            model = model.to(memory_format=torch.channels_last)
+        self.model = model
+        self.channels_last = bool(channels_last)
+        self.qconv = bool(qconv and channels_last and torch.cuda.is_available())
+        self.pack_bins = bool(pack_bins and self.qconv)
+        self.all_convs = [m for m in model.modules() if hasattr(m, "quantize_fn")]
+        self._office = hasattr(model, "feature") or hasattr(model, "feature_layers")
+        self._acc = None             # include/alignq.h: {double sum ce, int64 top-1, int64 top-5, int64 rows}
+        self._saved = None           # module flags and training modes to restore
+        self._wq = None              # the parked quantised filters (persistent: a captured graph reads them)
+        self._scope = None
+        self._init_capture(None)
+
+    # ------------------------------------------------------------------------------------------- lifecycle
+    def _set_flags(self):
+        m_all = list(self.model.modules())
+        self._saved = [(m, m.training, {f: m.__dict__.get(f, _MISSING) for f in _FLAGS}) for m in m_all]
+        for m in m_all:
+            if m.__dict__.get("_wq_stage") is not None:
+                m._wq_stage = None               # (OfficeTrainStep.stage_weights re-quantises per stage and batch)
+            if hasattr(m, "quantize_fn"):
+                m.use_qconv = self.qconv
+                m.emit_bn_stats = False          # no batch statistics in evaluation
+            if hasattr(m, "fuse_bn") or hasattr(m, "act_q0") or (hasattr(m, "act_q1") and hasattr(m, "act_q3")):
+                m.fuse_bn = self.channels_last
+                if self._office:
+                    m.fuse_relu = True
+            if self._office and hasattr(m, "act_q1") and hasattr(m, "act_q2") and hasattr(m, "act_q3"):
+                m.pack_bins = self.pack_bins
+            elif hasattr(m, "conv1") and hasattr(m, "act_q0") and hasattr(m, "bn0"):
+                m.pack_bins = self.pack_bins
+
+    def _restore_flags(self):
+        for m, training, flags in self._saved or ():
+            m.training = training
+            for f, v in flags.items():
+                if v is _MISSING:
+                    m.__dict__.pop(f, None)
+                else:
+                    m.__dict__[f] = v
+        self._saved = None
+
+    def _quantize_weights(self):
+        """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
+        evaluation refreshes the SAME tensors in place: a captured graph keeps reading them."""
+        convs = [c for c in self.all_convs if getattr(c.quantize_fn, "w_bit", 32) != 32 and hasattr(c.quantize_fn, "_pre")]
+        fused.prequantize_weights(convs, pack=self.qconv and self._office)
+        fresh = {id(c): c.quantize_fn._pre for c in convs}
+        if self._wq is not None and set(self._wq) == set(fresh):
+            for key, old in self._wq.items():
+                for o, n in zip(_flat(old[1:]), _flat(fresh[key][1:])):
+                    o.copy_(n)
+        else:
+            self._wq = fresh
+            self._graph = None           # (tensors a captured graph read are gone)
+        for c in convs:
+            c.quantize_fn._pre = self._wq[id(c)]
+            c.quantize_fn._pre_keep = True
+
+    def begin(self):
+        if self._saved is not None:
+            raise RuntimeError("EvalStep.begin: already begun (call end() first)")
+        self._set_flags()
+        try:
+            self.model.eval()
+            dev = next(self.model.parameters()).device
+            with torch.no_grad():
+                self._quantize_weights()
+                if self._acc is None or self._acc.device != dev:
+                    self._acc = torch.zeros(4, dtype=torch.int64, device=dev)
+                    self._graph = None
+                else:
+                    self._acc.zero_()
+        except BaseException:
+            self.end()              # (a failing __enter__ gets no __exit__: leave the model as it was)
+            raise
+        return self
+
+    def end(self):
+        for c in self.all_convs:
+            q = c.quantize_fn
+            if hasattr(q, "_pre"):
+                q._pre, q._pre_keep = None, False
+        self._restore_flags()
+        return self
+
+    __enter__ = begin
+
+    def __exit__(self, *exc):
+        self.end()
+        return False
+
+    # ------------------------------------------------------------------------------------------- one batch
+    def _logits(self, x):
+        m = self.model
+        if hasattr(m, "feature"):                      # DANN: class logits; alpha only scales the reversed gradient
+            feature, _ = m.feature(x)
+            return m.class_classifier(feature.view(-1, 2048))
+        if hasattr(m, "feature_layers"):               # DSAN: s_pred
+            feature, _ = m.feature_layers(x)
+            return m.cls_fc(m._head(feature))
+        out = m(x)
+        return out[0] if isinstance(out, tuple) else out
+
+    def _iteration(self, x, y, set_to_none=True):
+        if self._saved is None:
+            raise RuntimeError("EvalStep: call begin() first (or use the step as a context manager)")
+        if self.channels_last and x.dim() == 4:
+            x = x.contiguous(memory_format=torch.channels_last)
+        with torch.no_grad(), fused.eval_scope():
+            logits = self._logits(x)
+            self._metrics(logits, y)
+        return logits
+
+    def _metrics(self, logits, y):
+        lg = L.dev_f32(logits, "logits")
+        if y.dtype != torch.int64 or not y.is_cuda:
+            raise TypeError("EvalStep: targets must be a CUDA int64 tensor")
+        y = y.contiguous()
+        B, K = lg.shape
+        L.check(L.load().alignq_eval_metrics(L.ptr(lg), L.ptr(y), int(B), int(K), L.ptr(self._acc), L.stream_ptr()),
+                "alignq_eval_metrics")
+
+    def _eager_fallback(self, *inputs):
+        return self._iteration(*inputs)
+
+    def __call__(self, x, y):
+        if self._saved is None:      # (also in front of a replay: the graph reads this evaluation's filters and accumulator)
+            raise RuntimeError("EvalStep: call begin() first (or use the step as a context manager)")
+        return super().__call__(x, y)
+
+    def capture(self, x, y, warmup=2):
+        """Record the per-batch work (forward + metrics) as one HIP graph after `warmup` eager batches (allocator pools, MIOpen /
+        rocBLAS plans; at least one), on _CapturedStep's static buffers and warm-up; the warm-up batches do not count.  Later calls
+        with tensors of these shapes replay it; another batch size (a short last batch) runs eagerly."""
+        if self._saved is None:
+            raise RuntimeError("EvalStep.capture: call begin() first")
+        static = self._static_clones((x, y))
+        keep = self._acc.clone()
+        self._warm_up(static, max(int(warmup), 1))
+        self._acc.copy_(keep)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            outs = self._iteration(*static)
+        self._graph, self._graph2 = graph, None
+        self._static, self._outs = static, outs
+        return self
+
+    # ------------------------------------------------------------------------------------------- result
+    def counts(self):
+        """(sum of cross-entropy, top-1 count, top-5 count, rows) as accumulated: the evaluation's one host read"""
+        raw = self._acc.cpu().numpy()
+        return float(raw[:1].view(np.float64)[0]), int(raw[1]), int(raw[2]), int(raw[3])
+
+    def result(self):
+        """(mean cross-entropy, Prec@1, Prec@5, n) over the batches since begin().  Precisions in percent, like utils.accuracy."""
+        ce, n1, n5, n = self.counts()
+        if n == 0:
+            return float("nan"), 0.0, 0.0, 0
+        return ce / n, 100.0 * n1 / n, 100.0 * n5 / n, n
+
+
+def _flat(items):
+    for t in items:
+        if isinstance(t, (tuple, list)):
+            yield from _flat(t)
+        elif torch.is_tensor(t):
+            yield t

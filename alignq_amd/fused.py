@@ -722,6 +722,10 @@ def bn_site(bn, act, z, eps=0.0, relu=False, residual=None, pack=False):
     pack=True (N2; needs relu, no residual, channels-last, a_bit <= 8): `out` is a packed handle (see BNSiteFn.forward) whose
     values are int8 / int16 level indices; only hand it to Conv2d_Q (which reads the indices) or through `materialize`."""
     from . import config, ops
+    if _eval.on:
+        out = bn_site_eval(bn, act, z, relu, residual, pack)
+        if out is not None:
+            return out
     if not bn_site_fusable(bn, act, z) or (residual is not None and not (
             residual.shape == z.shape and residual.stride() == z.stride() and residual.dtype == torch.float32)):
         # not foldable (batch above 128 rows, the exact-global correlation, ...): the batch-norm alone still runs on the folded family's
@@ -931,9 +935,134 @@ def conv_partials(z, groups):
     return rec[0], rec[1]
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# The evaluation pass (eval_step.EvalStep; the reference's test(), e.g. cdf_alignment_admm/resnet-20-cifar-10/main.py:405-441):
+# eval-mode batch-norm (running statistics) + quantiser [+ shortcut] [+ ReLU] as ONE launch of alignq_bnq_eval_fwd per site.
+# At an ADMM site no Gram, no loss and no write to ADMM.D: test() discards them.
+class _EvalState(threading.local):
+    on = False
+
+
+_eval = _EvalState()
+
+
+class eval_scope:
+    """While active (per thread, like conv_groups_scope) bn_site / bn_act_relu / bn_only / bn_site_res_relu send an EVAL-mode
+    batch-norm to their `*_eval` counterparts below.  Only EvalStep enters it: a bare `model.eval(); model(x)` keeps today's
+    composition."""
+
+    def __enter__(self):
+        self.prev, _eval.on = _eval.on, True
+        return self
+
+    def __exit__(self, *exc):
+        _eval.on = self.prev
+        return False
+
+
+def eval_active() -> bool:
+    return _eval.on
+
+
+def _bn_eval_ok(bn, z, residual=None) -> bool:
+    """alignq_bnq_eval_fwd's domain: an eval-mode nn.BatchNorm2d with running statistics on a channels-last fp32 CUDA tensor,
+    C a power of two in [4, 2048] (the range of _bn_nhwc_ok), any batch."""
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and bn.running_mean is not None and bn.running_var is not None):
+        return False
+    if not (z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    C = z.shape[1]
+    if not (4 <= C <= 2048 and (C & (C - 1)) == 0 and z.numel() > 0):
+        return False
+    return residual is None or (residual.shape == z.shape and residual.is_cuda and residual.dtype == torch.float32)
+
+
+def bn_eval_fwd(bn, z, k, act_range, formula, relu=False, residual=None, pack_dtype=None):
+    """[relu]([act_q](bn.eval()(z)) [+ residual]) by one alignq_bnq_eval_fwd launch (k == 32: the batch-norm alone).  pack_dtype
+    (torch.int8 / torch.int16): the result is a packed handle carrying the level indices as `._alignq_bins`; else fp32, tagged
+    with its level count where the GEMM convolutions can use it.  The caller has checked `_bn_eval_ok`."""
+    lib = L.load()
+    B, C, H, W = z.shape
+    if residual is not None and residual.stride() != z.stride():
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    bins = y = None
+    if pack_dtype is not None:
+        bins = torch.empty(z.shape, dtype=pack_dtype, device=z.device, memory_format=torch.channels_last)
+    else:
+        y = torch.empty_like(z, memory_format=torch.channels_last)
+    rc = lib.alignq_bnq_eval_fwd(L.ptr(z), B * H * W, C, L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean),
+                                 L.ptr(bn.running_var), float(bn.eps), int(k), float(act_range), int(formula), int(bool(relu)),
+                                 L.ptr(residual), L.ptr(y), L.ptr(bins), 0 if bins is None else bins.element_size(), L.stream_ptr())
+    L.check(rc, "alignq_bnq_eval_fwd")
+    if bins is not None:
+        y = packed_handle(z.shape, z.device)
+        y._alignq_bins = (bins, int(k))
+    if residual is None and k != 32:
+        tag_levels(y, k, act_range, formula)
+    return y
+
+
+def _act_is_identity(act) -> bool:
+    """a_bit == 32 outside the 'align' stage: the quantiser modules return their input (quantization._plain_act / _site_act)"""
+    return getattr(act, "a_bit", 32) == 32 and getattr(act, "stage", None) != "align"
+
+
+def _eval_k(act):
+    """The quantiser's bit width for alignq_bnq_eval_fwd, 32 for an identity quantiser; None: no folded form (a_bit == 32 in the
+    'align' stage returns the transform, a width outside the kernels' 1..16)."""
+    if _act_is_identity(act):
+        return 32
+    a_bit = int(getattr(act, "a_bit", 32))
+    return a_bit if 1 <= a_bit <= 16 else None
+
+
+def bn_site_eval(bn, act, z, relu=False, residual=None, pack=False):
+    """bn_site's evaluation counterpart: (out, 0.0), or None where the kernel does not apply (the caller composes)."""
+    from . import config, ops
+    k = _eval_k(act)
+    if k is None or not _bn_eval_ok(bn, z, residual):
+        return None
+    pd = None
+    if pack and relu and residual is None and k <= 8 and z.numel() % 4 == 0:
+        pd = ops.bin_dtype(k, config.args.act_range, L.FORMULA_ADMM)
+    return bn_eval_fwd(bn, z, k, config.args.act_range, L.FORMULA_ADMM, relu, residual, pd), 0.0
+
+
+def bn_act_relu_eval(bn, act, z, formula, relu=True, residual=None, pack=False):
+    """bn_act_relu's evaluation counterpart (same packing conditions), or None."""
+    from . import config
+    k = _eval_k(act)
+    if k is None or not _bn_eval_ok(bn, z, residual):
+        return None
+    r = float(config.args.act_range)
+    pack = bool(pack and relu and residual is None and formula == L.FORMULA_ADMM and 1 <= k <= 14
+                and L.load().alignq_bin_bytes(k, r, int(formula)) == 2 and r * (2 ** k - 1) <= 2048.0 and r == int(r))
+    return bn_eval_fwd(bn, z, k, r, formula, relu, residual, torch.int16 if pack else None)
+
+
+def bn_only_eval(bn, z):
+    """bn_only's evaluation counterpart (k = 32: no quantiser), or None."""
+    if not _bn_eval_ok(bn, z):
+        return None
+    return bn_eval_fwd(bn, z, 32, 1.0, L.FORMULA_ADMM)
+
+
+def bn_site_res_relu_eval(bn, act, z, residual):
+    """The Office bottleneck's tail relu(act_q3(bn3(z))[0] + identity) in evaluation: (out, 0.0), or None."""
+    from . import config
+    k = _eval_k(act)
+    if k is None or residual is None or not _bn_eval_ok(bn, z, residual):
+        return None
+    return bn_eval_fwd(bn, z, k, config.args.act_range, L.FORMULA_ADMM, True, residual), 0.0
+
+
 def bn_only(bn, z, groups=1):
     """bn(z): the folded-family kernels when the tensor is channels-last fp32 in training mode, else the module itself
     (groups > 1: applied to the batch slices one after the other, as the reference's successive passes do)."""
+    if _eval.on and groups == 1:
+        out = bn_only_eval(bn, z)
+        if out is not None:
+            return out
     if not _bn_nhwc_ok(bn, z, groups):
         if groups == 1:
             return bn(z)
@@ -1211,6 +1340,10 @@ def bn_site_res_relu(bn, act, z, residual, eps, groups=1, loss_vec=False):
     it).  loss_vec (groups > 1): the loss comes back as the VECTOR of the slices' losses (a view, no kernel) for a caller that sums
     all its sites at once (resnet_office.ResNet.forward), instead of their sum."""
     from . import config
+    if _eval.on and groups == 1:
+        out = bn_site_res_relu_eval(bn, act, z, residual)
+        if out is not None:
+            return out
     if not (_bn_nhwc_ok(bn, z, groups) and 2 <= z.shape[0] // groups <= 32 and act.a_bit < 32
             and config.args.method == "ours"
             and active_deferred() is None and residual is not None and residual.shape == z.shape and residual.is_cuda
@@ -1269,6 +1402,10 @@ def bn_act_relu(bn, act, z, formula, relu=True, groups=1, residual=None, pack=Fa
     exactly): `out` is a packed handle (BNQuantReluFn.forward) whose values live in `out._alignq_bins = (int16 indices, a_bit)` -
     hand it to a Conv2d_Q only (anything else: fused.materialize)."""
     from . import config
+    if _eval.on and groups == 1:
+        out = bn_act_relu_eval(bn, act, z, formula, relu, residual, pack)
+        if out is not None:
+            return out
     res_ok = residual is None or (residual.shape == z.shape and residual.is_cuda and residual.dtype == torch.float32)
     if not (bnq_fusable(bn, act, z, groups) and res_ok):
         def one(zz, rr):

@@ -62,6 +62,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
             self.uniform_q = uniform_quantize(k=w_bit)
             self._formula = formula
             self._pre = None      # (weight, q, cdf, pdf) parked by fused.prequantize_weights for the next call
+            self._pre_keep = False
 
         def forward(self, x):
             if self.w_bit == 32:
@@ -69,7 +70,9 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     self.weight_cdf = x
                     self.weight_q = x
                 return x
-            pre, self._pre = self._pre, None
+            pre = self._pre
+            if not getattr(self, "_pre_keep", False):     # (EvalStep keeps the parked tensors for every batch of an evaluation: the filters do not change)
+                self._pre = None
             self._bins = None
             if pre is not None and pre[0] is x:
                 q, c, pdf = pre[1], pre[2], pre[3]

@@ -166,12 +166,13 @@ class _CapturedStep:
             raise RuntimeError(f"{who}: a parameter has no momentum buffer yet; run at least one eager iteration "
                                "(capture(..., warmup>=1)) before capturing the step")
 
-    def _capture(self, inputs, warmup):
-        who = f"{type(self).__name__}.capture"
-        release_step_graphs(self.admms)
-        assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], who)
-        static = tuple(t.clone(memory_format=torch.channels_last) if (self.channels_last and t.dim() == 4) else t.clone()
-                       for t in inputs)
+    def _static_clones(self, inputs):
+        """The buffers a captured graph reads: clones of `inputs`, images in the step's memory format."""
+        return tuple(t.clone(memory_format=torch.channels_last) if (self.channels_last and t.dim() == 4) else t.clone()
+                     for t in inputs)
+
+    def _warm_up(self, static, warmup):
+        """`warmup` eager iterations on a side stream (allocator pools, pointer tables, MIOpen plans), then a device synchronise."""
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -179,6 +180,13 @@ class _CapturedStep:
                 self._iteration(*static, set_to_none=False)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+
+    def _capture(self, inputs, warmup):
+        who = f"{type(self).__name__}.capture"
+        release_step_graphs(self.admms)
+        assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], who)
+        static = self._static_clones(inputs)
+        self._warm_up(static, warmup)
         self._assert_momentum_buffers(who)
         release_step_graphs(self.admms)          # (an unfused site of the warm-up keeps D with its graph)
         # inside the capture grads are re-created (set_to_none=True): no zero-fill and no accumulate-add per

@@ -706,6 +706,42 @@ int alignq_lmmd_fwd(const float* x_src, const float* x_tgt, const int64_t* s_lab
 int alignq_lmmd_bwd(const float* g, const float* x_src, const float* x_tgt, const void* ws, int B, int64_t D, float* dx_src,
                     float* dx_tgt, void* stream);
 
+/* ---- the evaluation pass: the reference's test() (cdf_alignment_admm/resnet-20-cifar-10/main.py:405-441, dann_office/main.py:502-545;
+ * accuracy: utils/common.py:78-92) - eval-mode batch-norm folded into the quantiser, metrics accumulated on the device
+ * (csrc/eval_kernels.hip; Python: alignq_amd/eval_step.py).
+ *
+ * alignq_bnq_eval_fwd: ONE elementwise pass per site,  y = [relu]( [act_q]( a_c z + b_c ) [+ residual] ),  in the order the reference
+ *   composes them (model/resnet.py: `out = act_q(bn(conv(x)))`, `out += shortcut`, `out = relu(out)`).  z: the convolution's output as
+ *   [P, C], channels fastest (torch.channels_last), C a power of two in [4, 2048] (ALIGNQ_EUNSUPPORTED otherwise), any P >= 1.
+ *   gamma / beta (either may be NULL = 1 / 0), running_mean, running_var: the batch-norm's [C] vectors; they are only READ.  Every
+ *   workgroup forms the coefficients itself; there is no statistics pass, no second launch and nothing is saved.
+ *   Arithmetic (fp32, every operation rounded on its own, no fused multiply-add):
+ *       s_c = sqrt(running_var_c + bn_eps);   a_c = gamma_c / s_c;   b_c = beta_c - (a_c * running_mean_c);   x = (a_c * z) + b_c
+ *   then x_q = the quantiser of alignq_act_quant_fwd (formula, act_range; NERF32: level indices bit-identical to oracle/alignq_oracle.c),
+ *   then `x_q + residual`, then relu(v) = v > 0 ? v : +0.  k == 32: NO quantiser, y = [relu](x [+ residual]) - the batch-norm alone
+ *   (the Office downsample branch, a site built with a_bit = 32).  (torch's eval-mode batch-norm computes (z - mean) / sqrt(var + eps)
+ *   * gamma + beta: same value to a few ulp.)
+ *   pack = 0: fp32 y.  pack = 1 / 2 (N2, the conditions of alignq_site_partials_bn bins_out / alignq_bnq_fwd_parts bins_out: ADMM /
+ *   Office formula, no residual, k <= 16, alignq_bin_bytes(k, act_range, ALIGNQ_FORMULA_ADMM) <= pack; else ALIGNQ_EINVAL): bins_out
+ *   receives the level index of the stored value (clamped at 0 when relu) as int8 / int16 in z's layout; y may then be NULL.
+ *   bins_out != NULL exactly when pack != 0.  16-byte aligned pointers.  Non-temporal stores from 2^25 elements.                   */
+int alignq_bnq_eval_fwd(const float* z, int64_t P, int C, const float* gamma, const float* beta, const float* running_mean,
+                        const float* running_var, float bn_eps, int k, float act_range, int formula, int relu,
+                        const float* residual, float* y, void* bins_out, int pack, void* stream);
+/* alignq_eval_metrics: one launch per batch.  logits [B, K] fp32, K <= 1024 (ALIGNQ_EUNSUPPORTED above), target [B] int64.  Per row:
+ *   ce = logsumexp(logits[row]) - logits[row][target]   and   rank = #{j : logits[row][j] > logits[row][target]}  (STRICTLY greater).
+ * acc: 32 caller-owned bytes of device memory, 8-byte aligned, zeroed by the caller before the first batch:
+ *   bytes  0.. 7  double   sum of ce
+ *   bytes  8..15  int64    rows with rank < 1   (Prec@1 = 100 * this / rows)
+ *   bytes 16..23  int64    rows with rank < 5   (Prec@5)
+ *   bytes 24..31  int64    rows seen (+= B per launch)
+ * The launch ADDS its batch to acc.  One workgroup sums the rows in row order and updates acc with plain stores: no atomics, so two
+ * runs over the same batches give the same bits; launches on one stream are ordered.  A row holding a NaN logit counts as wrong
+ * (its ce is NaN, as torch's).  A target outside [0, K) counts as wrong, adds nothing to the ce sum and reads nothing out of bounds.
+ * Ties: only classes strictly above the target's logit count, so a row whose target ties for first place is correct; torch.topk
+ * (utils/common.py:84) leaves the order of tied logits unspecified and may decide such a row either way.                          */
+int alignq_eval_metrics(const float* logits, const int64_t* target, int B, int K, void* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
