@@ -168,6 +168,11 @@ class EvalStep(_CapturedStep):
             raise RuntimeError("EvalStep: call begin() first (or use the step as a context manager)")
         return super().__call__(x, y)
 
+    def next(self):
+        if self._saved is None:
+            raise RuntimeError("EvalStep: call begin() first (or use the step as a context manager)")
+        return super().next()
+
     def capture(self, x, y, warmup=2):
         """Record the per-batch work (forward + metrics) as one HIP graph after `warmup` eager batches (allocator pools, MIOpen /
         rocBLAS plans; at least one), on _CapturedStep's static buffers and warm-up; the warm-up batches do not count.  Later calls
@@ -180,6 +185,7 @@ class EvalStep(_CapturedStep):
         self._acc.copy_(keep)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
+            self._record_inputs(static)
             outs = self._iteration(*static)
         self._graph, self._graph2 = graph, None
         self._static, self._outs = static, outs

@@ -88,6 +88,7 @@ class _CapturedStep:
         self._static = None                 # the input buffers the graphs read
         self._outs = None                   # the captured iteration's results
         self._recapture = False             # capture from the next eager call's inputs (new_epoch)
+        self._producer = None               # a loader whose fill is the first work of the (first) graph (set_producer)
 
     def _iteration(self, *inputs, set_to_none=True):
         outs = self._forward_backward(*inputs, set_to_none=set_to_none, overlap=True)
@@ -116,11 +117,17 @@ class _CapturedStep:
             # off-shape batch (the reference's loaders have no drop_last: CIFAR's last batch is 80 of 128): a captured
             # graph only fits its static shapes, so this one iteration runs eagerly
             return self._eager_fallback(*inputs)
+        if self._producer is not None:
+            raise RuntimeError(f"{type(self).__name__}: the captured graph fills its own inputs from the attached loader (a replay "
+                               "would overwrite the given tensors' copies); call next(), or capture without a producer")
         # a loader that writes its batches straight into `static_inputs()` (the target of its host-to-device copy) hands the
         # same tensors back: nothing to stage
         for x, s in zip(inputs, self._static):
             if x is not s:
                 s.copy_(x, non_blocking=True)
+        return self._replay()
+
+    def _replay(self):
         self._graph.replay()
         if self._graph2 is not None:
             # data-parallel: only the collectives run eagerly between the two captured halves (the buckets are packed in the
@@ -128,6 +135,36 @@ class _CapturedStep:
             self.grad_hook.reduce()
             self._graph2.replay()
         return self._outs
+
+    def set_producer(self, loader):
+        """Attach an input producer (alignq_amd.data.DeviceLoader; None detaches): the next `capture` records
+        `loader.record(*static_inputs)` - one batch launch, which also moves the cursor on - as the first node of the (first) graph, and
+        `next()` replays it: batch n of the epoch on the n-th call after `loader.begin_epoch`.  Without a producer every graph is
+        node for node what it was.  An existing capture is dropped (the step runs eagerly until `capture` is called again)."""
+        if loader is not None and not (hasattr(loader, "record") and hasattr(loader, "next_batch")):
+            raise TypeError("set_producer: expected a DeviceLoader")
+        self._producer = loader
+        self._graph = self._graph2 = None
+        return self
+
+    def next(self):
+        """The iteration on the attached loader's coming batch: one replay, no host work on the batch and no tensor passed.  The
+        short last batch of an epoch (the reference's loaders have no drop_last) is filled eagerly and takes the eager fallback."""
+        p = self._producer
+        if p is None or self._graph is None:
+            raise RuntimeError(f"{type(self).__name__}.next: needs set_producer(loader) and capture(...) first")
+        rows = p.next_batch_size()
+        if rows == 0:
+            raise RuntimeError(f"{type(self).__name__}.next: the loader's epoch is exhausted; call loader.begin_epoch")
+        if rows != self._static[0].shape[0]:
+            return self._eager_fallback(*p.next_batch())
+        p.skip(rows)
+        return self._replay()
+
+    def _record_inputs(self, static):
+        """Inside a capture, in front of the iteration: the producer's batch launch into the graph's input buffers."""
+        if self._producer is not None:
+            self._producer.record(*static)
 
     def static_inputs(self):
         """The buffers the captured graph reads ((x, y) or (xs, ys, xt); images in the step's memory format).  Fill them in
@@ -212,6 +249,7 @@ class _CapturedStep:
         self._graph2 = None
         if not split:
             with torch.cuda.graph(graph, **cap_mode):
+                self._record_inputs(static)
                 outs = self._iteration(*static, set_to_none=True)
         else:
             # data parallel: forward + backward (+ the buckets packed) | eager all-reduces | bucket unpack + optimizer steps
@@ -220,6 +258,7 @@ class _CapturedStep:
             # (dp.GradAndDAllReduce): every bucket is packed behind the backward.
             overlapped = hasattr(hook, "capture_begin")
             with torch.cuda.graph(graph, **cap_mode):
+                self._record_inputs(static)
                 if overlapped:
                     hook.capture_begin()
                 outs = self._forward_backward(*static, set_to_none=True, overlap=False)
@@ -453,6 +492,10 @@ class OfficeTrainStep(_CapturedStep):
         # (source batch, target batch, device), so the ones a captured graph reads outlive an off-shape eager iteration
         self._dom_labels = {}
         self._init_capture(grad_hook)
+
+    def set_producer(self, loader):
+        raise NotImplementedError("the Office steps (224 x 224 inputs decoded from JPEG files) take their batches from the caller; "
+                                  "alignq_amd.data covers the 32 x 32 byte-image sets")
 
     def _backbone(self):
         """The ResNet feature extractor (DANN: `feature`)."""

@@ -742,6 +742,36 @@ int alignq_bnq_eval_fwd(const float* z, int64_t P, int C, const float* gamma, co
  * (utils/common.py:84) leaves the order of tied logits unspecified and may decide such a row either way.                          */
 int alignq_eval_metrics(const float* logits, const int64_t* target, int B, int K, void* acc, void* stream);
 
+/* ---- the input pipeline: the reference's torchvision loaders (cdf_alignment_admm/resnet-20-cifar-10/data/cifar10.py:11-33 -
+ * RandomCrop(32, padding=4), RandomHorizontalFlip(), ToTensor(), Normalize(mean, std), shuffle, no drop_last - and
+ * cdf_alignment/resnet-20-svhn/data/svhn.py:14-34 - ToTensor(), Normalize) on the device (csrc/data_kernels.hip; Python:
+ * alignq_amd/data.py).  The data set stays in device memory as bytes; one launch produces one batch.
+ *
+ * alignq_data_batch: images [N][32][32][3] bytes (HWC: the array torchvision's CIFAR10.data holds), labels [N] int64, perm [N] int64 =
+ *   the sample order of this epoch, or NULL = identity (a test set).  cursor: DEVICE memory, three int32 {epoch, first position of this
+ *   batch, 0}, read by the kernel, so one captured launch serves every batch of every epoch.  advance = 0: the cursor is only read.
+ *   advance > 0: once every workgroup of the launch has read it, the launch sets cursor[1] += advance (the workgroups count themselves
+ *   in cursor[2], which the last one leaves at 0 again), so the next launch on the stream, or the next replay of a graph holding this
+ *   one, produces the next batch; the host writes {epoch, 0, 0} only when an epoch begins.  lut [3][256] fp32: the normalised value of byte
+ *   v in channel c, built by the host in exactly the arithmetic of ToTensor + Normalize (v / 255 - mean_c) / std_c in fp32; the kernel is a
+ *   pure gather and does no floating-point arithmetic.
+ *   Row i of the batch takes sample s = perm[pos], pos = cursor[1] + rank * B + i (data parallel: a global batch is world * B consecutive
+ *   positions).  A row with pos outside [0, N) (or a perm entry outside [0, N)) is NOT written: neither x_out nor y_out.
+ *   Random draws: a stateless function of (seed, epoch = cursor[0] as uint32, pos); all arithmetic on uint64, modulo 2^64:
+ *       mix64(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *       key = mix64(mix64(seed) + epoch);      r = mix64(key + 0x9E3779B97F4A7C15 * (pos + 1))
+ *       dy = ((r & 0xFFFFFF) * 9) >> 24;       dx = (((r >> 24) & 0xFFFFFF) * 9) >> 24;       f = (r >> 48) & 1
+ *   dy, dx in 0..8 (torchvision draws randint(0, 40 - 32 + 1) per axis) when pad == 4, else 0; f only when flip, else 0.  The same
+ *   (seed, epoch, pos) gives the same crop whatever B, rank or world: an epoch does not depend on how it is cut into batches.
+ *   Output pixel (c, h, w) reads source pixel (h + dy - pad, w' + dx - pad), w' = 31 - w if f else w (crop first, then flip).  Outside the
+ *   image the BYTE is 0 (the reference pads the uint8 image before ToTensor / Normalize): the value is lut[c][0], not 0.0.
+ *   x_out: [B, 3, 32, 32] fp32, contiguous (nhwc = 0) or the same shape in channels-last storage (nhwc = 1); y_out[i] = labels[s].
+ *   pad in {0, 4}, flip / nhwc in {0, 1}, 0 <= rank < world, B >= 1, N >= 1, advance >= 0, lut and x_out 16-byte aligned; else ALIGNQ_EINVAL, before
+ *   anything touches a device.  N <= 2^30, B <= 65535, advance <= 2^30 (ALIGNQ_EUNSUPPORTED above).                                  */
+int alignq_data_batch(const uint8_t* images, const int64_t* labels, const int64_t* perm, int32_t* cursor, int advance, const float* lut,
+                      int64_t N, int B, int rank, int world, uint64_t seed, int pad, int flip, float* x_out, int nhwc, int64_t* y_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
