@@ -184,6 +184,10 @@ SIGNATURES = {
     "alignq_sgd_step_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _f, _f, _vp]),
     "alignq_sgd_admm_step_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _f, _f,
                                         _i, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),
+    "alignq_sgd_step_multi_dev": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _f, _f, _vp]),
+    "alignq_sgd_admm_step_multi_dev": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _f, _f,
+                                            _i, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),
+    "alignq_hyper_advance": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "alignq_lmmd_ws_bytes": (_sz, [_i, _i64]),
     "alignq_lmmd_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _c.c_double, _i, _c.c_double, _vp, _vp, _vp]),
     "alignq_lmmd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),

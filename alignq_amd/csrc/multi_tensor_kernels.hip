@@ -342,6 +342,54 @@ __global__ __launch_bounds__(kAdmmThreads) void mt_sgd_admm_kernel(SAChunk c, in
   }
 }
 
+// The same two kernels with the learning rate and a "fresh optimizer" flag read from DEVICE memory (alignq_amd/schedule.py: one row of
+// floats that a captured graph's nodes share), so one captured step serves every rate of a schedule (MultiStepLR: resnet-20-cifar-10/
+// main.py:97,126; the per-epoch SGD of dann_office/main.py:321-328) instead of being captured again.  Both values sit at addresses
+// every lane shares, behind const __restrict__ kernel-argument pointers: the compiler loads them with scalar loads into scalar
+// registers, so `use_buf` stays a block-uniform condition (no per-load branches; same registers and branch count as the by-value
+// kernels).  sgd_tensor is the by-value kernels' body: same arithmetic.
+__device__ __forceinline__ bool fresh_flag(const float* __restrict__ fresh_dev) {
+  return fresh_dev != nullptr && *fresh_dev != 0.0f;
+}
+
+__global__ __launch_bounds__(kThreads) void mt_sgd_dev_kernel(SChunk c, const float* __restrict__ lr_dev,
+                                                              const float* __restrict__ fresh_dev, float mom, float damp, float wd,
+                                                              int nesterov, float nlev, float lam, float lam2) {
+  const int t = blockIdx.y;
+  const float lr = *lr_dev;
+  const bool first = c.first[t] != 0 || fresh_flag(fresh_dev);
+  sgd_tensor<kThreads>(c.p[t], c.g[t], c.buf[t], c.cdf[t], c.pdf[t], c.n[t], first, lr, mom, damp, wd, nesterov, nlev, lam, lam2);
+}
+
+__global__ __launch_bounds__(kAdmmThreads) void mt_sgd_admm_dev_kernel(SAChunk c, int T, const float* __restrict__ lr_dev,
+                                                                       const float* __restrict__ fresh_dev, float mom, float damp,
+                                                                       float wd, int nesterov, float nlev, float lam, float lam2, int b,
+                                                                       int dim, float mu, float rho) {
+  __shared__ double sm[48];
+  const int t = blockIdx.y;
+  if (t < T) {
+    const float lr = *lr_dev;
+    const bool first = c.first[t] != 0 || fresh_flag(fresh_dev);
+    sgd_tensor<kAdmmThreads>(c.p[t], c.g[t], c.buf[t], c.cdf[t], c.pdf[t], c.n[t], first, lr, mom, damp, wd, nesterov, nlev, lam,
+                             lam2);
+  } else if (blockIdx.x == 0) {
+    const int s = t - T;
+    admm_update_site(c.D[s], c.A[s], c.G[s], b, dim, mu, rho, sm);
+  }
+}
+
+// alignq_hyper_advance: row min(*cursor, rows - 1) of a row-major table into row_out, then *cursor += 1 (one workgroup of 64)
+constexpr int kHyperCols = 64;
+__global__ __launch_bounds__(kHyperCols) void hyper_advance_kernel(const float* __restrict__ table, int rows, int cols,
+                                                                   int32_t* cursor, float* __restrict__ row_out) {
+  const int c = *cursor;                   // every thread reads it before the barrier, one writes it behind
+  int r = c < rows - 1 ? c : rows - 1;
+  if (r < 0) r = 0;
+  if ((int)threadIdx.x < cols) row_out[threadIdx.x] = table[(long)r * cols + threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x == 0) *cursor = c + 1;
+}
+
 inline int blocks_for(long max_n) {
   long b = (max_n + 2047) / 2048;
   if (b < 1) b = 1;
@@ -518,6 +566,84 @@ int alignq_sgd_admm_step_multi(int T, float* const* p, float* const* g, float* c
   if (bx > kMaxBlk) bx = kMaxBlk;
   hipLaunchKernelGGL(mt_sgd_admm_kernel, dim3((unsigned)bx, T + S), kAdmmThreads, 0, (hipStream_t)stream, c, T, lr, mom, damp, wd,
                      nesterov, nlev, lam, lam2, b, dim, mu, rho);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int alignq_sgd_step_multi_dev(int T, float* const* p, float* const* g, float* const* buf, const int64_t* n,
+                              const float* const* w_cdf, const float* const* w_pdf, const int32_t* first, const float* lr_dev,
+                              const float* fresh_dev, float mom, float damp, float wd, int nesterov, int bitW, float lam,
+                              float lam2, void* stream) {
+  if (T <= 0 || !p || !g || !n || !lr_dev) return ALIGNQ_EINVAL;
+  if (mom != 0.0f && !buf) return ALIGNQ_EINVAL;
+  if (bitW < 1 || bitW > 30) bitW = 1;
+  const float nlev = (float)((1 << bitW) - 1);
+  hipStream_t st = (hipStream_t)stream;
+  for (int t0 = 0; t0 < T; t0 += kSgdChunk) {
+    const int cnt = (T - t0 < kSgdChunk) ? T - t0 : kSgdChunk;
+    SChunk c;
+    long max_n = 0;
+    for (int i = 0; i < cnt; i++) {
+      if (!p[t0 + i] || !g[t0 + i] || n[t0 + i] <= 0) return ALIGNQ_EINVAL;
+      if (mom != 0.0f && !buf[t0 + i]) return ALIGNQ_EINVAL;
+      c.p[i] = p[t0 + i]; c.g[i] = g[t0 + i]; c.buf[i] = buf ? buf[t0 + i] : nullptr;
+      c.cdf[i] = (w_cdf && w_pdf && w_cdf[t0 + i] && w_pdf[t0 + i]) ? w_cdf[t0 + i] : nullptr;
+      c.pdf[i] = c.cdf[i] ? w_pdf[t0 + i] : nullptr;
+      c.n[i] = (long)n[t0 + i];
+      c.first[i] = (first && first[t0 + i]) ? 1 : 0;
+      if (c.n[i] > max_n) max_n = c.n[i];
+    }
+    dim3 grid(blocks_for(max_n), cnt);
+    hipLaunchKernelGGL(mt_sgd_dev_kernel, grid, kThreads, 0, st, c, lr_dev, fresh_dev, mom, damp, wd, nesterov, nlev, lam, lam2);
+    LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int alignq_sgd_admm_step_multi_dev(int T, float* const* p, float* const* g, float* const* buf, const int64_t* n,
+                                   const float* const* w_cdf, const float* const* w_pdf, const int32_t* first, const float* lr_dev,
+                                   const float* fresh_dev, float mom, float damp, float wd, int nesterov, int bitW, float lam,
+                                   float lam2, int S, const float* const* D_tab, float* const* alterD_tab, float* const* gamma_tab,
+                                   int b, int dim, float mu, float rho, void* stream) {
+  if (T <= 0 || !p || !g || !n || !lr_dev || S <= 0 || !D_tab || !alterD_tab || !gamma_tab || b <= 0 || dim < b) return ALIGNQ_EINVAL;
+  if (mom != 0.0f && !buf) return ALIGNQ_EINVAL;
+  if (dim > 4096) return ALIGNQ_EUNSUPPORTED;
+  if (T > kSgdA || S > kSiteA) {       // as alignq_sgd_admm_step_multi: the two launches of the separate entry points
+    if (int rc = alignq_sgd_step_multi_dev(T, p, g, buf, n, w_cdf, w_pdf, first, lr_dev, fresh_dev, mom, damp, wd, nesterov, bitW, lam,
+                                           lam2, stream))
+      return rc;
+    return alignq_admm_update(D_tab, alterD_tab, gamma_tab, S, b, dim, mu, rho, stream);
+  }
+  if (bitW < 1 || bitW > 30) bitW = 1;
+  const float nlev = (float)((1 << bitW) - 1);
+  SAChunk c;
+  long max_n = 0;
+  for (int i = 0; i < T; i++) {
+    if (!p[i] || !g[i] || n[i] <= 0) return ALIGNQ_EINVAL;
+    if (mom != 0.0f && !buf[i]) return ALIGNQ_EINVAL;
+    c.p[i] = p[i]; c.g[i] = g[i]; c.buf[i] = buf ? buf[i] : nullptr;
+    c.cdf[i] = (w_cdf && w_pdf && w_cdf[i] && w_pdf[i]) ? w_cdf[i] : nullptr;
+    c.pdf[i] = c.cdf[i] ? w_pdf[i] : nullptr;
+    c.n[i] = (long)n[i];
+    c.first[i] = (first && first[i]) ? 1 : 0;
+    if (c.n[i] > max_n) max_n = c.n[i];
+  }
+  for (int i = 0; i < S; i++) {
+    if (!D_tab[i] || !alterD_tab[i] || !gamma_tab[i]) return ALIGNQ_EINVAL;
+    c.D[i] = D_tab[i]; c.A[i] = alterD_tab[i]; c.G[i] = gamma_tab[i];
+  }
+  long bx = (max_n + (long)kAdmmThreads * kU - 1) / ((long)kAdmmThreads * kU);
+  if (bx < 1) bx = 1;
+  if (bx > kMaxBlk) bx = kMaxBlk;
+  hipLaunchKernelGGL(mt_sgd_admm_dev_kernel, dim3((unsigned)bx, T + S), kAdmmThreads, 0, (hipStream_t)stream, c, T, lr_dev, fresh_dev,
+                     mom, damp, wd, nesterov, nlev, lam, lam2, b, dim, mu, rho);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int alignq_hyper_advance(const float* table, int rows, int cols, int32_t* cursor, float* row_out, void* stream) {
+  if (!table || !cursor || !row_out || rows < 1 || cols < 1 || cols > kHyperCols) return ALIGNQ_EINVAL;
+  hipLaunchKernelGGL(hyper_advance_kernel, dim3(1), dim3(kHyperCols), 0, (hipStream_t)stream, table, rows, cols, cursor, row_out);
   LAUNCH_CHECK();
   return 0;
 }

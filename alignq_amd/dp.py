@@ -142,6 +142,7 @@ def attach(train_step, group=None, force=False, global_corr=False):
     global_corr=True (opt-in): every ADMM site computes the correlation pair of the GLOBAL batch
     (global_corr below; the model's ADMM(dim) must have been built with the global batch size, <= 1024: above 128 rows the blocked Gram of corr_large_kernels.hip) instead of the
     per-rank [b,b] matrices; BN fold and deferred site launches are switched off for it (the sites run unfused)."""
+    train_step._refuse_hook_with_hyper(True, train_step._hyper is not None)      # before anything is changed
     if global_corr:
         # scoped to THIS model's quantiser modules (not the process-global config): other models / steps in the process keep
         # the per-rank semantics; detach() restores what is changed here
@@ -448,6 +449,7 @@ class BucketedGradAllReduce:
 def attach_office(office_step, group=None, force=False, bucket_bytes=24 << 20, min_buckets=4):
     """Wire data parallelism into an OfficeTrainStep: broadcast the initial state, install the bucketed, overlapped
     all-reduce over every parameter SGD steps (feature extractor incl. alterD / gamma, both heads) + the sites' D."""
+    office_step._refuse_hook_with_hyper(True, office_step._hyper is not None)    # before anything is changed
     broadcast_module_state(office_step.model, 0, group)
     params = [p for g in office_step.optimizer_t.param_groups for p in g["params"]]
     hook = BucketedGradAllReduce(params, lambda: [b.admm0.D for b in office_step.blocks], group, force=force,

@@ -31,17 +31,36 @@ class SGD(Optimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov))
+        self._hyper = None
+
+    def attach_hyper(self, block):
+        """Read the learning rates (and the `fresh` flag) from `block` (alignq_amd.schedule.HyperBlock: one rate slot per parameter
+        group, in order) instead of passing group["lr"] by value: the launches go to the `_dev` entry points, so a captured step
+        follows whatever the block holds at replay time.  Every momentum buffer is created here (zeros): a buffer is then never
+        born inside a capture, and "this step starts the momentum afresh" (a new SGD in the reference, utils/optimizer.py:222-224)
+        is the block's `fresh` slot, under which the kernel does not read the buffer."""
+        if block.n_groups != len(self.param_groups):
+            raise ValueError(f"SGD.attach_hyper: the block has {block.n_groups} rate slots, the optimizer {len(self.param_groups)} "
+                             "parameter groups")
+        for group in self.param_groups:
+            if group["momentum"] != 0:
+                for p in group["params"]:
+                    if "momentum_buffer" not in self.state[p]:
+                        self.state[p]["momentum_buffer"] = torch.zeros_like(p)
+        self._hyper = block
+        return self
 
     def __setstate__(self, state):
         super().__setstate__(state)
         for group in self.param_groups:
             group.setdefault("nesterov", False)
+        self.__dict__.setdefault("_hyper", None)
 
     def _gather(self, idx, w_cdf, w_pdf):
         """Per parameter group: (hyper-parameters, tensors of the multi-tensor launch); creates missing momentum buffers."""
         bitW = int(config.args.bitW)
         out = []
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             wd, mom, damp, nest, lr = (group["weight_decay"], group["momentum"], group["dampening"],
                                        group["nesterov"], group["lr"])
             ps, gs, bufs, firsts, cdfs, pdfs = [], [], [], [], [], []
@@ -66,16 +85,18 @@ class SGD(Optimizer):
                     c, pdf = L.like_layout(w_cdf[j].detach(), p, "w_cdf"), L.like_layout(w_pdf[j].detach(), p, "w_pdf")
                 ps.append(p); gs.append(g); bufs.append(buf); firsts.append(first); cdfs.append(c); pdfs.append(pdf)
             if ps:
-                out.append(((float(lr), float(mom), float(damp), float(wd), int(bool(nest))), ps, gs, bufs, firsts, cdfs, pdfs))
+                out.append(((float(lr), float(mom), float(damp), float(wd), int(bool(nest))), ps, gs, bufs, firsts, cdfs, pdfs, gi))
         return out
 
     @staticmethod
-    def _c_args(item):
-        """The argument prefix alignq_sgd_step_multi and alignq_sgd_admm_step_multi share."""
-        (lr, mom, damp, wd, nest), ps, gs, bufs, firsts, cdfs, pdfs = item
+    def _c_args(item, hyper=None):
+        """The argument prefix alignq_sgd_step_multi and alignq_sgd_admm_step_multi share; with `hyper` (a HyperBlock) that of
+        their `_dev` forms: the group's rate slot and the `fresh` slot as device pointers in place of the rate."""
+        (lr, mom, damp, wd, nest), ps, gs, bufs, firsts, cdfs, pdfs, gi = item
+        rate = (lr,) if hyper is None else (L.ptr(hyper.lr(gi)), L.ptr(hyper.fresh))
         return (len(ps), L.ptr_array(ps), L.ptr_array(gs), L.ptr_array(bufs) if mom != 0 else None,
-                L.i64_array([p.numel() for p in ps]), L.ptr_array(cdfs), L.ptr_array(pdfs), L.i32_array(firsts), lr, mom, damp,
-                wd, nest, min(int(config.args.bitW), 30))
+                L.i64_array([p.numel() for p in ps]), L.ptr_array(cdfs), L.ptr_array(pdfs), L.i32_array(firsts)) + rate + \
+            (mom, damp, wd, nest, min(int(config.args.bitW), 30))
 
     @torch.no_grad()
     def step(self, idx, w_cdf, w_pdf, lam, lam2, closure=None):
@@ -91,8 +112,13 @@ class SGD(Optimizer):
         memory the kernel must overwrite, not read): whoever gathers must launch THESE items, never gather again."""
         lib = L.load()
         st = L.stream_ptr()
+        hyper = self._hyper
         for item in items:
             # one multi-tensor launch (per <=72 tensors) for the whole group: step + p.grad rewrite for idx members
+            if hyper is not None:
+                L.check(lib.alignq_sgd_step_multi_dev(*self._c_args(item, hyper), float(lam), float(lam2), st),
+                        "alignq_sgd_step_multi_dev")
+                continue
             L.check(lib.alignq_sgd_step_multi(*self._c_args(item), float(lam), float(lam2), st), "alignq_sgd_step_multi")
 
 
@@ -172,10 +198,12 @@ def sgd_admm_step(sgd, sgd_args, admm, admm_args):
             items = sgd._gather(idx, w_cdf, w_pdf)
             assert len(items) == 1
             ((mu, rho, b, dim), sites), = groups.items()
-            L.check(L.load().alignq_sgd_admm_step_multi(
-                *SGD._c_args(items[0]), float(lam), float(lam2), len(sites), L.ptr_array([s_[0] for s_ in sites]),
+            hyper = sgd._hyper
+            name = "alignq_sgd_admm_step_multi" if hyper is None else "alignq_sgd_admm_step_multi_dev"
+            L.check(getattr(L.load(), name)(
+                *SGD._c_args(items[0], hyper), float(lam), float(lam2), len(sites), L.ptr_array([s_[0] for s_ in sites]),
                 L.ptr_array([s_[1] for s_ in sites]), L.ptr_array([s_[2] for s_ in sites]), b, dim, mu, rho, L.stream_ptr()),
-                "alignq_sgd_admm_step_multi")
+                name)
             return
     sgd.step(idx, w_cdf, w_pdf, lam, lam2)
     admm.step(alterD_idx, gamma_idx, Ds, alterDs, gammas, mus, rhos)

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from . import config
 from .fused import DeferredLosses, DeferredWgrads, HeadCEFn, head_ce_supported, prequantize_weights
 from .optimizer import ADMM_OPT, SGD, sgd_admm_step
+from .schedule import HyperBlock, Schedule, office_rate, ramp
 
 
 _PROBE = "alignq_capture_probe"
@@ -81,8 +82,21 @@ class _CapturedStep:
     its __init__ and supplies `_forward_backward(*inputs, set_to_none, overlap)` (overlap=True: an eager iteration, which runs
     the grad_hook itself) and `_optimizer_steps()`."""
 
-    def _init_capture(self, grad_hook):
+    def _init_capture(self, grad_hook, device_hyper=False, **slots):
+        """device_hyper: the learning rates (and the `slots`: alpha / coef) live in a device row (alignq_amd.schedule.HyperBlock)
+        the optimizer kernels read at run time, so set_lr / new_epoch / a per-iteration alpha keep a captured graph."""
+        self._hyper = None                  # the HyperBlock (device_hyper=True)
         self.grad_hook = grad_hook          # e.g. the data-parallel all-reduce (alignq_amd.dp)
+        self._schedule = None               # a table that alignq_hyper_advance walks, one row per iteration (set_schedule)
+        self._fresh_pending = False         # the row says fresh = 1 and no iteration has consumed it yet
+        if device_hyper:
+            self._refuse_hook_with_hyper(grad_hook, True)
+            dev = next(self.model.parameters()).device
+            self._hyper = HyperBlock(dev, len(self.optimizer_t.param_groups))
+            self.optimizer_t.attach_hyper(self._hyper)
+            # a new optimizer: the first iteration starts the momentum (utils/optimizer.py:222-224)
+            self._hyper.set(lr=[g["lr"] for g in self.optimizer_t.param_groups], fresh=1, **slots)
+            self._fresh_pending = True
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._graph2: Optional[torch.cuda.CUDAGraph] = None
         self._static = None                 # the input buffers the graphs read
@@ -90,7 +104,19 @@ class _CapturedStep:
         self._recapture = False             # capture from the next eager call's inputs (new_epoch)
         self._producer = None               # a loader whose fill is the first work of the (first) graph (set_producer)
 
+    def _refuse_hook_with_hyper(self, hook, hyper):
+        """Data parallelism splits the capture around the eager all-reduce: the table's node and the hand-over of `fresh` are only
+        defined for the one-graph step."""
+        if hook is not None and hyper:
+            raise NotImplementedError(f"{type(self).__name__}: device_hyper=True with a grad_hook (data parallel: alignq_amd.dp.attach "
+                                      "/ attach_office) is not covered")
+
     def _iteration(self, *inputs, set_to_none=True):
+        if self._hyper is not None:
+            # (a hook can be installed by assignment after the step was built; dp.attach / attach_office refuse it themselves)
+            self._refuse_hook_with_hyper(self.grad_hook, True)
+        if self._schedule is not None:
+            self._schedule.advance()        # this iteration's row; inside a capture: the node in front of the iteration
         outs = self._forward_backward(*inputs, set_to_none=set_to_none, overlap=True)
         self._optimizer_steps()
         return _detached(outs)
@@ -106,9 +132,59 @@ class _CapturedStep:
         else:
             torch.autograd.backward(roots, grads)
 
+    def _consumed(self):
+        """Behind every iteration that has been enqueued (eager, warm-up, fallback or replay; never inside a capture): the one
+        iteration that was to start the momentum afresh has done so - the row is staged again with fresh = 0.  (With a table
+        the rows carry `fresh` themselves.)"""
+        if self._fresh_pending:
+            self._fresh_pending = False
+            if self._schedule is None:
+                self._hyper.set(fresh=0)
+
+    def _need_hyper(self, what):
+        if self._hyper is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: needs a step built with device_hyper=True")
+
+    def set_schedule(self, table):
+        """Drive the row from `table` (float32 [iterations, n_groups + 3]: alignq_amd.schedule.multistep / office_dann /
+        office_dsan): every iteration first launches alignq_hyper_advance - row min(cursor, rows - 1) into the
+        row, cursor + 1 - eagerly or, after `capture`, as a node in front of the iteration (behind the producer's).  The cursor
+        therefore counts the iterations run, warm-ups included (`seek`).  A run is then replays with no host write at all;
+        set_lr, a per-call alpha / lambd and new_epoch's staging are the table's business and refused or skipped.  Call it
+        before `capture`: an existing capture is dropped.  A table is not detached again (the row would keep its last
+        values while the host's mirror holds older ones): attach another table, or build a new step."""
+        self._need_hyper("set_schedule")
+        if table is None:
+            raise ValueError(f"{type(self).__name__}.set_schedule: a schedule table cannot be detached; attach another one or "
+                             "build a new step")
+        self._schedule = Schedule(self._hyper, table)
+        self._graph = self._graph2 = None
+        self._fresh_pending = False
+        return self
+
+    def _host_stages(self, what):
+        if self._schedule is not None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: the schedule table owns the row (set_schedule); put the value into "
+                               "the table")
+
+    def seek(self, i):
+        """The next iteration reads row `i` of the table (e.g. after the warm-up, or resuming a run)."""
+        if self._schedule is None:
+            raise RuntimeError(f"{type(self).__name__}.seek: no schedule table (set_schedule)")
+        self._schedule.seek(i)
+        return self
+
+    def current_hyper(self):
+        """The device row (lr per group, alpha, coef, fresh) and the table's cursor (None without one): one host read, for logs."""
+        self._need_hyper("current_hyper")
+        out = self._hyper.read()
+        out["cursor"] = None if self._schedule is None else self._schedule.position()
+        return out
+
     def __call__(self, *inputs):
         if self._graph is None:
             outs = self._iteration(*inputs)
+            self._consumed()
             if self._recapture:
                 self._recapture = False
                 self.capture(*inputs, warmup=0)
@@ -128,7 +204,10 @@ class _CapturedStep:
         return self._replay()
 
     def _replay(self):
+        if self._hyper is not None:
+            self._refuse_hook_with_hyper(self.grad_hook, True)
         self._graph.replay()
+        self._consumed()
         if self._graph2 is not None:
             # data-parallel: only the collectives run eagerly between the two captured halves (the buckets are packed in the
             # first graph and unpacked at the start of the second)
@@ -183,7 +262,9 @@ class _CapturedStep:
         hook = self.grad_hook
         keep_hook = hook.snapshot() if hasattr(hook, "snapshot") else None
         try:
-            return self._iteration(*inputs)
+            outs = self._iteration(*inputs)
+            self._consumed()
+            return outs
         finally:
             for p, g in zip(params, keep_g):
                 p.grad = g
@@ -198,6 +279,8 @@ class _CapturedStep:
         step updates to own its buffer already, i.e. at least one eager step since the optimizer was created."""
         opt = self.optimizer_t
         momentum = [p for g in opt.param_groups if g["momentum"] != 0 for p in g["params"]]
+        if self._hyper is not None and all("momentum_buffer" in opt.state[p] for p in momentum):
+            return                  # (SGD.attach_hyper created every buffer; the row's `fresh` slot starts the momentum)
         if momentum and (all(p.grad is None for g in opt.param_groups for p in g["params"])
                          or any(p.grad is not None and "momentum_buffer" not in opt.state[p] for p in momentum)):
             raise RuntimeError(f"{who}: a parameter has no momentum buffer yet; run at least one eager iteration "
@@ -215,11 +298,13 @@ class _CapturedStep:
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self._iteration(*static, set_to_none=False)
+                self._consumed()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
 
     def _capture(self, inputs, warmup):
         who = f"{type(self).__name__}.capture"
+        self._refuse_hook_with_hyper(self.grad_hook, self._hyper is not None)      # before the warm-up touches the model
         release_step_graphs(self.admms)
         assert_no_retained_graph([p for g in self.optimizer_t.param_groups for p in g["params"]], who)
         static = self._static_clones(inputs)
@@ -278,8 +363,10 @@ class _CapturedStep:
 
 class TrainStep(_CapturedStep):
     def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=1e-4, grad_hook=None, defer_losses=True, fuse_bn=True,
-                 channels_last=False, qconv=True, pack_bins=True):
-        """channels_last: keep activations and conv weights in torch.channels_last memory (values, parameter names and
+                 channels_last=False, qconv=True, pack_bins=True, device_hyper=False):
+        """device_hyper: the learning rate in device memory (alignq_amd.schedule): set_lr keeps a captured graph, and
+        set_schedule lets the graph walk a MultiStepLR table by itself.
+        channels_last: keep activations and conv weights in torch.channels_last memory (values, parameter names and
         state_dict are unchanged).  MIOpen's NHWC convolution kernels need no layout transposes around the weight-gradient
         igemm (2.22 vs 2.50 ms per ResNet-20 step on MI355X); the quantise / Gram / ADMM kernels are layout-agnostic and the
         BN fold has a channels-last form."""
@@ -323,7 +410,7 @@ class TrainStep(_CapturedStep):
                 self.admms += [layer.admm0, layer.admm1]
                 if layer.skip_conv is not None:
                     self.admms.append(layer.admm_skip)
-        self._init_capture(grad_hook)
+        self._init_capture(grad_hook, device_hyper)
         self._one = None
 
     # -------------------------------------------------------------------------------------------
@@ -394,7 +481,14 @@ class TrainStep(_CapturedStep):
     def set_lr(self, lr):
         """The reference steps a StepLR scheduler once per epoch (main.py:112,150).  Scalar hyper-parameters are baked into
         a captured graph as kernel arguments, so a captured step is re-captured (no warm-up iterations: the model is not
-        touched) whenever the learning rate changes."""
+        touched) whenever the learning rate changes.  With device_hyper the rate is staged into the device row the optimizer
+        kernel reads (one 16-byte copy, none if unchanged) and the graph stays."""
+        if self._hyper is not None:
+            self._host_stages("set_lr")
+            for g in self.optimizer_t.param_groups:
+                g["lr"] = lr
+            self._hyper.set(lr=lr)
+            return self
         changed = False
         for g in self.optimizer_t.param_groups:
             changed |= g["lr"] != lr
@@ -432,8 +526,10 @@ class OfficeTrainStep(_CapturedStep):
     SGD-stepped first and then overwritten by the closed form, exactly like the reference."""
 
     def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=5e-4, alpha=0.5, channels_last=False, fuse_relu=True,
-                 grad_hook=None, fuse_bn=True, dual=None, qconv=True, pack_bins=True):
-        """grad_hook: the data-parallel all-reduce (alignq_amd.dp.attach_office -> BucketedGradAllReduce): begin() right
+                 grad_hook=None, fuse_bn=True, dual=None, qconv=True, pack_bins=True, device_hyper=False):
+        """device_hyper: the three group rates, alpha and the "new SGD" flag in device memory (alignq_amd.schedule): new_epoch
+        and a per-iteration alpha (dann_office/main.py:346-348) keep one captured graph.
+        grad_hook: the data-parallel all-reduce (alignq_amd.dp.attach_office -> BucketedGradAllReduce): begin() right
         before backward, its buckets' collectives start from autograd hooks while the backward runs, finish() before the
         optimizer steps.
         channels_last: activations and conv weights in torch.channels_last memory (values / names unchanged): MIOpen's NHWC
@@ -491,7 +587,28 @@ class OfficeTrainStep(_CapturedStep):
         # the domain labels (main.py:360-361 builds them every iteration) are constants of the batch sizes: kept per
         # (source batch, target batch, device), so the ones a captured graph reads outlive an off-shape eager iteration
         self._dom_labels = {}
-        self._init_capture(grad_hook)
+        self._init_capture(grad_hook, device_hyper, **self._hyper_slots())
+
+    def _hyper_slots(self):
+        """What the row holds besides the rates when the step is built."""
+        return dict(alpha=self.alpha)
+
+    def _alpha(self):
+        """ReverseLayerF's factor: the number, or (device_hyper) the row's slot, which the backward multiplies by as a tensor."""
+        return self.alpha if self._hyper is None else self._hyper.alpha
+
+    def __call__(self, xs, ys, xt, alpha=None):
+        """alpha: the gradient-reversal coefficient of this iteration (train_step.dann_alpha; None: the value in force, at first
+        the constructor's).  A captured graph can only follow it through the device row."""
+        if alpha is not None:
+            if self._hyper is not None:
+                self._host_stages("__call__(alpha=...)")
+                self._hyper.set(alpha=alpha)
+            elif self._graph is not None:
+                raise RuntimeError(f"{type(self).__name__}: the captured graph holds alpha as a constant; build the step with "
+                                   "device_hyper=True to change it per iteration")
+            self.alpha = alpha
+        return super().__call__(xs, ys, xt)
 
     def set_producer(self, loader):
         raise NotImplementedError("the Office steps (224 x 224 inputs decoded from JPEG files) take their batches from the caller; "
@@ -560,13 +677,13 @@ class OfficeTrainStep(_CapturedStep):
         m = self.model
         label_src, label_tgt = labels
         if self.dual and xs.shape == xt.shape:
-            cls_s, dom_s, dom_t, tl_both = m.forward_dual(xs, xt, alpha=self.alpha)      # (same weights, hence the same W_q,
+            cls_s, dom_s, dom_t, tl_both = m.forward_dual(xs, xt, alpha=self._alpha())      # (same weights, hence the same W_q,
             tl_s, tl_t = tl_both, 0.0                                                    #  in both of the reference's passes)
         else:
-            cls_s, dom_s, tl_s = m(xs, alpha=self.alpha)
+            cls_s, dom_s, tl_s = m(xs, alpha=self._alpha())
             if not self._staged:
                 prequantize_weights(self.all_convs, pack=self.qconv)      # the reference quantises every weight once per pass
-            _, dom_t, tl_t = m(xt, alpha=self.alpha)
+            _, dom_t, tl_t = m(xt, alpha=self._alpha())
         # (a pass without a loss tensor contributes the NUMBER 0: adding it would be an elementwise launch of its own)
         tl = tl_s if not torch.is_tensor(tl_t) and tl_t == 0 else (tl_t if not torch.is_tensor(tl_s) and tl_s == 0 else tl_s + tl_t)
         loss = F.cross_entropy(cls_s, ys) + F.cross_entropy(dom_s, label_src) + F.cross_entropy(dom_t, label_tgt) + tl
@@ -583,8 +700,21 @@ class OfficeTrainStep(_CapturedStep):
     def new_epoch(self, epoch, num_epochs, lr, momentum=0.9, weight_decay=5e-4):
         """dann_office/main.py:321-328: every epoch the reference builds a NEW SGD (so momentum buffers start from scratch)
         with LEARNING_RATE = lr / (1 + 10 (epoch-1) / num_epochs)^0.75 for the two heads and a tenth of it for the feature
-        extractor.  A captured step is re-captured (graph kernel arguments hold the learning rates)."""
-        rate = lr / (1.0 + 10.0 * (epoch - 1) / num_epochs) ** 0.75
+        extractor.  A captured step is re-captured (graph kernel arguments hold the learning rates).
+        With device_hyper the optimizer object and the graph stay: the group rates and fresh = 1 are staged into the device row,
+        and the next iteration - of whatever kind - starts every momentum buffer from its gradient, as a new SGD does."""
+        rate = office_rate(lr, epoch, num_epochs)
+        if self._hyper is not None:
+            rates = []
+            for g, spec in zip(self.optimizer_t.param_groups, self._param_groups(rate)):
+                if g["momentum"] != momentum or g["weight_decay"] != weight_decay:
+                    raise NotImplementedError("new_epoch(device_hyper): momentum and weight decay are arguments of the captured kernels")
+                g["lr"] = spec.get("lr", rate / 10)
+                rates.append(g["lr"])
+            if self._schedule is None:          # (a table's rows carry the epoch's rates and fresh = 1 themselves)
+                self._hyper.set(lr=rates, fresh=1)
+                self._fresh_pending = True
+            return rate
         self.optimizer_t = SGD(self._param_groups(rate), lr=rate / 10, momentum=momentum, weight_decay=weight_decay)
         if self._graph is not None:
             # the first step of the epoch creates the fresh momentum buffers (buf = grad) and must not be the captured one
@@ -596,12 +726,16 @@ class OfficeTrainStep(_CapturedStep):
         return self._capture((xs, ys, xt), warmup)
 
 
+def dann_alpha(num_iters, num_epochs, num_iterations):
+    """cdf_alignment_admm/dann_office/main.py:345-348: the gradient-reversal coefficient of global iteration `num_iters` (=
+    num_iterations * epoch + i, i counting from 1) of a run of `num_epochs` epochs with `num_iterations` iterations each."""
+    return ramp(num_iters, num_epochs, num_iterations)
+
+
 def dsan_lambd(num_iters, num_epochs, num_iterations):
     """cdf_alignment_admm/dsan_office/main.py:381-382: the LMMD ramp for global iteration `num_iters` (= num_iterations *
     epoch + i) of a run of `num_epochs` epochs with `num_iterations` iterations each."""
-    import numpy as np
-    p = float(num_iters) / num_epochs / num_iterations
-    return 2. / (1. + np.exp(-10 * p) + 1e-6) - 1
+    return ramp(num_iters, num_epochs, num_iterations)
 
 
 class DSANTrainStep(OfficeTrainStep):
@@ -613,11 +747,16 @@ class DSANTrainStep(OfficeTrainStep):
     iteration of the ramp.  Not covered: data parallelism, src_only_flag."""
 
     def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=5e-4, channels_last=False, fuse_relu=True, fuse_bn=True,
-                 dual=None, qconv=True, pack_bins=True):
+                 dual=None, qconv=True, pack_bins=True, device_hyper=False):
         super().__init__(model, lr=lr, momentum=momentum, weight_decay=weight_decay, channels_last=channels_last,
-                         fuse_relu=fuse_relu, fuse_bn=fuse_bn, dual=dual, qconv=qconv, pack_bins=pack_bins)
+                         fuse_relu=fuse_relu, fuse_bn=fuse_bn, dual=dual, qconv=qconv, pack_bins=pack_bins,
+                         device_hyper=device_hyper)
         dev = next(self.model.parameters()).device
-        self._coef = torch.zeros(1, dtype=torch.float32, device=dev)     # args.param * lambd of the coming iteration
+        # args.param * lambd of the coming iteration (device_hyper: the row's `coef` slot)
+        self._coef = torch.zeros(1, dtype=torch.float32, device=dev) if self._hyper is None else self._hyper.coef
+
+    def _hyper_slots(self):
+        return dict(coef=0.0)
 
     def _backbone(self):
         return self.model.feature_layers
@@ -631,7 +770,11 @@ class DSANTrainStep(OfficeTrainStep):
 
     def set_lambd(self, lambd):
         """Stage args.param * lambd (main.py:407, formed in Python floats as there) for the next iteration: one fill, no sync."""
-        self._coef.fill_(float(config.args.param * lambd))
+        if self._hyper is not None:
+            self._host_stages("set_lambd")
+            self._hyper.set(coef=float(config.args.param * lambd))
+        else:
+            self._coef.fill_(float(config.args.param * lambd))
 
     def _domain_labels(self, xs, xt):
         return None                        # (no domain classifier)
@@ -646,9 +789,14 @@ class DSANTrainStep(OfficeTrainStep):
             s_pred, loss_mmd = m(xs, xt, ys)
         return s_pred, F.cross_entropy(s_pred, ys) + self._coef * loss_mmd, loss_mmd
 
-    def __call__(self, xs, ys, xt, lambd):
-        """(s_pred, loss, loss_mmd) of the iteration; lambd: dsan_lambd(...) of this iteration."""
-        self.set_lambd(lambd)
+    def __call__(self, xs, ys, xt, lambd=None):
+        """(s_pred, loss, loss_mmd) of the iteration; lambd: dsan_lambd(...) of this iteration.  It may only be left out when a
+        schedule table supplies args.param * lambd (set_schedule)."""
+        if lambd is None:
+            if self._schedule is None:
+                raise TypeError("DSANTrainStep.__call__: lambd is required (only a schedule table, set_schedule, replaces it)")
+        else:
+            self.set_lambd(lambd)
         return super().__call__(xs, ys, xt)
 
     def capture(self, xs, ys, xt, warmup=2, lambd=None):

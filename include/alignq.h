@@ -239,6 +239,32 @@ int alignq_sgd_admm_step_multi(int T, float* const* p, float* const* g, float* c
                                const float* const* D_tab, float* const* alterD_tab, float* const* gamma_tab, int b,
                                int dim, float mu, float rho, void* stream);
 
+/* ---- device-side hyper-parameters (exports added at ABI 23): the learning rate and a "fresh optimizer" flag read from DEVICE
+ * memory, so one captured graph follows a schedule without being captured again.
+ * alignq_sgd_step_multi_dev = alignq_sgd_step_multi with `lr` replaced by lr_dev (ONE device float, NULL: ALIGNQ_EINVAL) and fresh_dev
+ * (one device float or NULL).  Serves MultiStepLR (resnet-20-cifar-10/main.py:97,126: scheduler.step per epoch) and the SGD the
+ * Office trees build anew every epoch (dann_office/main.py:321-328, dsan_office/main.py:316-329: new group rates, momentum
+ * buffers from scratch): tensor t is `first` when first[t] != 0 || (fresh_dev && *fresh_dev != 0), and a first step does not read
+ * its momentum buffer (utils/optimizer.py:222-224: buf = clone(d_p)), whatever it holds.  Same arithmetic, chunking (72 tensors
+ * per launch) and error codes as the by-value entry point; bit-equal results for equal values.                                    */
+int alignq_sgd_step_multi_dev(int T, float* const* p, float* const* g, float* const* buf, const int64_t* n,
+                              const float* const* w_cdf, const float* const* w_pdf, const int32_t* first, const float* lr_dev,
+                              const float* fresh_dev, float mom, float damp, float wd, int nesterov, int bitW, float lam,
+                              float lam2, void* stream);
+/* alignq_sgd_admm_step_multi with the same replacement (resnet-20-cifar-10/main.py:97,126 and :330-340); more than 66 parameters or
+ * 22 sites fall back to alignq_sgd_step_multi_dev + alignq_admm_update.                                                           */
+int alignq_sgd_admm_step_multi_dev(int T, float* const* p, float* const* g, float* const* buf, const int64_t* n,
+                                   const float* const* w_cdf, const float* const* w_pdf, const int32_t* first, const float* lr_dev,
+                                   const float* fresh_dev, float mom, float damp, float wd, int nesterov, int bitW, float lam,
+                                   float lam2, int S, const float* const* D_tab, float* const* alterD_tab, float* const* gamma_tab,
+                                   int b, int dim, float mu, float rho, void* stream);
+/* One row of a schedule per iteration, inside the graph: c = *cursor; row_out[0..cols) = table[min(c, rows - 1)][0..cols) (row-major
+ * DEVICE table); *cursor = c + 1.  Past the end the last row repeats while the cursor keeps counting (the host can see the
+ * overrun).  The rows hold what the reference recomputes on the host: the epoch's rates (resnet-20-cifar-10/main.py:126;
+ * dann_office/main.py:321), DANN's alpha (dann_office/main.py:346-348) and DSAN's args.param * lambd (dsan_office/main.py:381-382,
+ * 410) of every iteration.  cols <= 64; rows < 1 or a NULL pointer: ALIGNQ_EINVAL.                                                 */
+int alignq_hyper_advance(const float* table, int rows, int cols, int32_t* cursor, float* row_out, void* stream);
+
 /* ---- all ADMM sites of a model in one launch each (64 < B <= 128): the slab reduction + loss of every site is off the
  * network's critical path (only x_q feeds the next layer), so a whole-model step can defer them to the end of the forward;
  * likewise ONE prep launch at the start of the backward.  Arrays are HOST arrays of S entries (passed by value to the
