@@ -31,6 +31,27 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
+// Diagnostic build only (-DALIGNQ_STAMPS, `make stamps`, never shipped; as in site4_kernels.hip): wall-clock stamps (100 MHz) of
+// ONE workgroup per role at phase boundaries (STAMP: `on` selects the workgroup), and every workgroup's entry / exit time of the
+// one-launch backward (BSTAMP), written to buffers no kernel reads.  Slots: 0-5 conv3x3_body forward, 8-13 its data-gradient
+// form (entry, loads issued, tile staged, filter ready, MFMA done, stored); 16 filter-gradient entry, 17 prologue done,
+// 18 + 2 i / 19 + 2 i tile i staged / its MFMA phase done (i < 16), 50 accumulators final, 51 slab stored.
+#ifdef ALIGNQ_STAMPS
+__device__ unsigned long long g_conv_stamps[64];
+__device__ unsigned long long g_conv_blk[2][4096];
+#define STAMP(on, i)                                                          \
+  do {                                                                        \
+    if ((on) && threadIdx.x == 0) g_conv_stamps[i] = wall_clock64();          \
+  } while (0)
+#define BSTAMP(which)                                                                          \
+  do {                                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < 4096) g_conv_blk[which][blockIdx.x] = wall_clock64(); \
+  } while (0)
+#else
+#define STAMP(on, i) do { } while (0)
+#define BSTAMP(which) do { } while (0)
+#endif
+
 // 4 pixels x 16 channels block at `p` (this lane's row q = (lane & 15) >> 2, columns 4 * (lane & 3)), transposed: the lane
 // receives channel (lane & 15) of the 4 pixels.  EXEC must be all ones (it is: no divergence around the calls).
 __device__ __forceinline__ s16x4 tr_read(const __bf16* p) {
@@ -168,6 +189,11 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int row0 = block * TR;                // first (image*H + h) row of this tile
   const int img_lo = (row0 / H) * H, img_hi = img_lo + H;       // rows of the tile's image
+  [[maybe_unused]] constexpr int SB = DGRAD ? 8 : 0;           // stamp slots of this form (diagnostic build)
+  STAMP(block == 0, SB + 0);
+  const int cog = wv % NCG, pp = wv / NCG;
+  const int m = lane & 15, q = lane >> 4;
+  bf16x8 ab[NS];               // integer bins of the quantised filter: exact in bf16
   // ---- stage the input tile (+ halo) as three bf16 terms; padding and out-of-image rows are zeros --------------------
   {
     constexpr int C4 = C / 4;
@@ -184,6 +210,7 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
       const f32x4 ld = fetch_act4<XB>(x, off);
       v[it] = ok ? make_float4(ld[0], ld[1], ld[2], ld[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    STAMP(block == 0, SB + 1);
     if (DGRAD && lazy.z) {       // x is g: turn it into the batch-norm input gradient here (zeros stay zeros: padding)
       float4 zz[NIT];
 #pragma unroll
@@ -238,65 +265,96 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
         *reinterpret_cast<bf16x4*>(Xlo + o) = l4;
       }
     }
-  }
-  // ---- filter fragments of this wave's 16-channel group: A[m = out channel][k = (tap, in channel)] ------------------
-  const int cog = wv % NCG, pp = wv / NCG;
-  const int m = lane & 15, q = lane >> 4;
-  bf16x8 ab[NS];               // integer bins of the quantised filter: exact in bf16
-#pragma unroll
-  for (int s = 0; s < NS; s++) {
-    const int k0 = 32 * s + 8 * q;
-    const int tap = k0 / C, c0 = k0 % C;
-    float v[8];
-    if (tap < 9) {
-      if (!DGRAD) {          // forward: W[co][tap][ci], 8 consecutive ci
-        const float* p = w + ((int64_t)(cog * 16 + m) * 9 + tap) * C + c0;
-        const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
-        v[0] = a4.x; v[1] = a4.y; v[2] = a4.z; v[3] = a4.w; v[4] = b4.x; v[5] = b4.y; v[6] = b4.z; v[7] = b4.w;
-      } else {               // data gradient: A[m = ci][k = (tap', co)] = W[co][8 - tap'][ci]
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = w[((int64_t)(c0 + j) * 9 + (8 - tap)) * C + cog * 16 + m];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; j++) v[j] = 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf(v[j] * nlev);
-  }
-  __syncthreads();
-  // ---- MFMA over this wave's pixel groups ----------------------------------------------------------------------------
-  float bs[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};   // batch-norm statistics of this lane's outputs
-  for (int g = pp; g < NG; g += NPP) {
-    const int p = g * 16 + (lane & 15);          // pixel of the tile owned by this lane (B column)
-    const int r = p / WD, c = p % WD;            // tile row / column
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    STAMP(block == 0, SB + 2);
+    // ---- filter fragments of this wave's 16-channel group, A[m][k = (tap, channel)], fetched behind the staged tile: unconditional
+    //      loads on clamped addresses (a k step past the ninth tap reads tap 8 and is zeroed).  Requesting them together with the
+    //      tile or ahead of it was measured and brings nothing (NOTES.md): issuing them takes 0.5 - 3 us, they are bound by their
+    //      volume per workgroup, not by latency, and ahead of the tile they delay it (the memory counter returns in order).
 #pragma unroll
     for (int s = 0; s < NS; s++) {
       const int k0 = 32 * s + 8 * q;
-      const int tap = k0 / C, c0 = k0 % C;
-      bf16x8 bh, bm, bl;
-      if (tap < 9) {
-        const int ky = tap / 3, kx = tap % 3;
-        const int o = ((r + ky) * LW + (c + kx)) * CP + c0;
-        bh = *reinterpret_cast<const bf16x8*>(Xhi + o);
-        bm = *reinterpret_cast<const bf16x8*>(Xmi + o);
-        bl = *reinterpret_cast<const bf16x8*>(Xlo + o);
-      } else {
+      const bool live = k0 / C < 9;
+      const int tap = live ? k0 / C : 8, c0 = k0 % C;
+      float wr[8];
+      if (!DGRAD) {          // forward: W[co][tap][ci], 8 consecutive ci
+        const float* p = w + ((int64_t)(cog * 16 + m) * 9 + tap) * C + c0;
+        const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
+        wr[0] = a4.x; wr[1] = a4.y; wr[2] = a4.z; wr[3] = a4.w; wr[4] = b4.x; wr[5] = b4.y; wr[6] = b4.z; wr[7] = b4.w;
+      } else {               // data gradient: A[m = ci][k = (tap', co)] = W[co][8 - tap'][ci]
 #pragma unroll
-        for (int j = 0; j < 8; j++) { bh[j] = (__bf16)0.f; bm[j] = (__bf16)0.f; bl[j] = (__bf16)0.f; }
+        for (int j = 0; j < 8; j++) wr[j] = w[((int64_t)(c0 + j) * 9 + (8 - tap)) * C + cog * 16 + m];
       }
-      // smallest terms first: the fp32 accumulator then loses the least (an integer index is exact in two terms: its third
-      // term is zero and its MFMA is skipped, a wave-uniform branch)
-      if (DGRAD || xb == 0) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bh, acc, 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
     }
+    STAMP(block == 0, SB + 3);
+  }
+  __syncthreads();
+  // ---- MFMA over this wave's pixel groups ----------------------------------------------------------------------------
+  // The wave's GW pixel groups run side by side, one accumulator each, and the B fragments of k step s + 1 (all groups) are
+  // requested before the MFMAs of step s (register double buffer): the LDS latency hides under the matrix pipe instead of
+  // standing between every read and its MFMA.  Per accumulator the sequence is unchanged: lo, mid, hi per step, steps ascending.
+  constexpr int GW = NG / NPP;                 // pixel groups per wave
+  static_assert(NG % NPP == 0, "every wave takes the same number of pixel groups");
+  int bo[GW];                                  // LDS element offset of each group's pixel (tap (0, 0), channel 0)
+  f32x4 acc[GW];
+#pragma unroll
+  for (int gi = 0; gi < GW; gi++) {
+    const int p = (pp + gi * NPP) * 16 + (lane & 15);      // pixel of the tile owned by this lane (B column)
+    bo[gi] = ((p / WD) * LW + (p % WD)) * CP;
+    acc[gi] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // GB groups at a time.  The forward launches have the registers for all of them (at most two workgroups per CU are needed);
+  // the data-gradient form shares its launch with the filter-gradient role and stays inside that kernel's register budget.
+  constexpr int GB = (DGRAD && GW > 2) ? 2 : GW;
+  static_assert(GW % GB == 0, "whole batches of groups");
+#pragma unroll
+  for (int g0 = 0; g0 < GW; g0 += GB) {
+    bf16x8 bh[2][GB], bm[2][GB], bl[2][GB];
+#pragma unroll
+    for (int s = 0; s <= NS; s++) {
+      if (s < NS) {
+        const int k0 = 32 * s + 8 * q;
+        const bool live = k0 / C < 9;
+        const int tap = live ? k0 / C : 8, c0 = k0 % C;
+        const int to = ((tap / 3) * LW + (tap % 3)) * CP + c0;
+#pragma unroll
+        for (int gi = 0; gi < GB; gi++) {
+          const int o = bo[g0 + gi] + to;
+          bh[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xhi + o);
+          bm[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xmi + o);
+          if (DGRAD || xb == 0) bl[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xlo + o);
+          if ((9 * C) % 32 != 0 && !live) {      // (the filter bins of such a step are zero as well)
+#pragma unroll
+            for (int j = 0; j < 8; j++) { bh[s & 1][gi][j] = (__bf16)0.f; bm[s & 1][gi][j] = (__bf16)0.f; bl[s & 1][gi][j] = (__bf16)0.f; }
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);       // (the compiler otherwise sinks the reads back in front of their MFMAs)
+      if (s > 0) {
+        const int u = s - 1;
+#pragma unroll
+        for (int gi = 0; gi < GB; gi++) {
+          // smallest terms first: the fp32 accumulator then loses the least (an integer index is exact in two terms: its third
+          // term is zero and its MFMA is skipped)
+          f32x4 a = acc[g0 + gi];
+          if (DGRAD || xb == 0) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bl[u & 1][gi], a, 0, 0, 0);
+          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bm[u & 1][gi], a, 0, 0, 0);
+          acc[g0 + gi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bh[u & 1][gi], a, 0, 0, 0);
+        }
+      }
+    }
+  }
+  float bs[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};   // batch-norm statistics of this lane's outputs
+#pragma unroll
+  for (int gi = 0; gi < GW; gi++) {              // groups in ascending order, as the statistics are summed
+    const int p = (pp + gi * NPP) * 16 + (lane & 15);
+    const int r = p / WD, c = p % WD;            // tile row / column
     const int grow = row0 + r;
     if (grow < total_rows) {
       const int64_t o = ((int64_t)grow * WD + c) * C + cog * 16 + 4 * q;
       const float den = (!DGRAD && xb != 0) ? nlev * xlev : nlev;        // integers <= 255 * 65535: exact in fp32 up to 2^24
-      float4 v = make_float4(acc[0] / den, acc[1] / den, acc[2] / den, acc[3] / den);
+      float4 v = make_float4(acc[gi][0] / den, acc[gi][1] / den, acc[gi][2] / den, acc[gi][3] / den);
       if (add) {       // e.g. the identity shortcut's gradient joining the data gradient (saves an accumulation kernel)
         const float4 r = *reinterpret_cast<const float4*>(add + o);
         v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
@@ -306,6 +364,7 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
       bq[0] += v.x * v.x; bq[1] += v.y * v.y; bq[2] += v.z * v.z; bq[3] += v.w * v.w;
     }
   }
+  STAMP(block == 0, SB + 4);
   // ---- optional epilogue: per-workgroup, per-channel {sum z, sum z^2} of the tile just produced, so that the batch-norm
   //      that follows needs no pass of its own over z.  Row (16-lane) sums on the DPP path, waves through LDS, fixed order.
   if (!DGRAD && bn_part) {
@@ -339,6 +398,7 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
       bn_part[((int64_t)tid * n_wg + block) * 2 + 1] = s1;
     }
   }
+  STAMP(block == 0, SB + 5);
 }
 
 template <int C, int WD, int PT, bool DGRAD, int XB = 0>
@@ -382,6 +442,9 @@ __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, co
   const int row0 = block * TR;                                   // first OUTPUT row (image*H + h) of the tile
   const int Hin = H * S;
   const int img_lo = (row0 / H) * Hin, img_hi = img_lo + Hin;    // INPUT rows of the tile's image
+  const int cog = wv % NCG, pp = wv / NCG;
+  const int m = lane & 15, q = lane >> 4;
+  bf16x8 ab[NS];
   {
     constexpr int C4 = CIN / 4;
     constexpr int N4 = LROWS * LW * C4;
@@ -418,53 +481,72 @@ __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, co
         *reinterpret_cast<bf16x4*>(Xlo + o) = l4;
       }
     }
-  }
-  const int cog = wv % NCG, pp = wv / NCG;
-  const int m = lane & 15, q = lane >> 4;
-  bf16x8 ab[NS];
 #pragma unroll
-  for (int s = 0; s < NS; s++) {
-    const int k0 = 32 * s + 8 * q;
-    const int tap = k0 / CIN, c0 = k0 % CIN;
-    if (tap < KS * KS) {
+    for (int s = 0; s < NS; s++) {             // filter fragments behind the staged tile (see conv3x3_body): unconditional, clamped
+      const int k0 = 32 * s + 8 * q;
+      const bool live = k0 / CIN < KS * KS;
+      const int tap = live ? k0 / CIN : KS * KS - 1, c0 = k0 % CIN;
       const float* p = w + ((int64_t)(cog * 16 + m) * (KS * KS) + tap) * CIN + c0;
       const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
-      const float v[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
+      const float wr[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf(v[j] * nlev);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)0.f;
+      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
     }
   }
   __syncthreads();
-  float bs[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int g = pp; g < NG; g += NPP) {
-    const int p = g * 16 + (lane & 15);
+  // MFMA phase as in conv3x3_body: the wave's pixel groups side by side, the fragments of step s + 1 requested before the
+  // MFMAs of step s; per accumulator lo, mid, hi per step, steps ascending
+  constexpr int GW = NG / NPP;
+  static_assert(NG % NPP == 0, "every wave takes the same number of pixel groups");
+  int bo[GW];
+  f32x4 acc[GW];
+#pragma unroll
+  for (int gi = 0; gi < GW; gi++) {
+    const int p = (pp + gi * NPP) * 16 + (lane & 15);
     const int r = p / WDO, c = p % WDO;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    bo[gi] = (KS == 3 ? (r * S * LW + c * S) : (r * LW + c)) * CP;
+    acc[gi] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  bf16x8 bh[2][GW], bm[2][GW], bl[2][GW];
 #pragma unroll
-    for (int s = 0; s < NS; s++) {
+  for (int s = 0; s <= NS; s++) {
+    if (s < NS) {
       const int k0 = 32 * s + 8 * q;
-      const int tap = k0 / CIN, c0 = k0 % CIN;
-      bf16x8 bh, bm, bl;
-      if (tap < KS * KS) {
-        const int ky = tap / KS, kx = tap % KS;
-        const int o = (KS == 3 ? ((r * S + ky) * LW + (c * S + kx)) : (r * LW + c)) * CP + c0;
-        bh = *reinterpret_cast<const bf16x8*>(Xhi + o);
-        bm = *reinterpret_cast<const bf16x8*>(Xmi + o);
-        bl = *reinterpret_cast<const bf16x8*>(Xlo + o);
-      } else {
+      const bool live = k0 / CIN < KS * KS;
+      const int tap = live ? k0 / CIN : KS * KS - 1, c0 = k0 % CIN;
+      const int to = (KS == 3 ? ((tap / KS) * LW + (tap % KS)) * CP : 0) + c0;
 #pragma unroll
-        for (int j = 0; j < 8; j++) { bh[j] = (__bf16)0.f; bm[j] = (__bf16)0.f; bl[j] = (__bf16)0.f; }
+      for (int gi = 0; gi < GW; gi++) {
+        const int o = bo[gi] + to;
+        bh[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xhi + o);
+        bm[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xmi + o);
+        bl[s & 1][gi] = *reinterpret_cast<const bf16x8*>(Xlo + o);
+        if ((KS * KS * CIN) % 32 != 0 && !live) {
+#pragma unroll
+          for (int j = 0; j < 8; j++) { bh[s & 1][gi][j] = (__bf16)0.f; bm[s & 1][gi][j] = (__bf16)0.f; bl[s & 1][gi][j] = (__bf16)0.f; }
+        }
       }
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], bh, acc, 0, 0, 0);
     }
+    __builtin_amdgcn_sched_barrier(0);
+    if (s > 0) {
+      const int u = s - 1;
+#pragma unroll
+      for (int gi = 0; gi < GW; gi++) {
+        f32x4 a = acc[gi];
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bl[u & 1][gi], a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bm[u & 1][gi], a, 0, 0, 0);
+        acc[gi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[u], bh[u & 1][gi], a, 0, 0, 0);
+      }
+    }
+  }
+  float bs[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int gi = 0; gi < GW; gi++) {
+    const int p = (pp + gi * NPP) * 16 + (lane & 15);
+    const int r = p / WDO, c = p % WDO;
     const int grow = row0 + r;
     if (grow < total_rows) {
-      const float4 v = make_float4(acc[0] / nlev, acc[1] / nlev, acc[2] / nlev, acc[3] / nlev);
+      const float4 v = make_float4(acc[gi][0] / nlev, acc[gi][1] / nlev, acc[gi][2] / nlev, acc[gi][3] / nlev);
       *reinterpret_cast<float4*>(y + ((int64_t)grow * WDO + c) * COUT + cog * 16 + 4 * q) = v;
       bs[0] += v.x; bs[1] += v.y; bs[2] += v.z; bs[3] += v.w;
       bq[0] += v.x * v.x; bq[1] += v.y * v.y; bq[2] += v.z * v.z; bq[3] += v.w * v.w;
@@ -1026,6 +1108,8 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
   const int cob = CB == 32 ? (wv >> 1) : 0, cib = CB == 32 ? (wv & 1) : 0;
   const int g = lane >> 4, q = (lane & 15) >> 2, pcol = 4 * (lane & 3);
 
+  [[maybe_unused]] const bool st_on = bx == 0 && by == 0;      // the stamped workgroup (diagnostic build)
+  STAMP(st_on, 16);
   f32x4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1081,6 +1165,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
       lk1 = *reinterpret_cast<const f32x4*>(lazy.ktot + COUT + cq);
     }
   }
+  STAMP(st_on, 17);
   for (int tile = t_begin; tile < t_end; tile++) {
     __syncthreads();                               // previous tile's readers are done
 #pragma unroll
@@ -1125,6 +1210,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
       }
     }
     __syncthreads();
+    STAMP(st_on && tile - t_begin < 16, 18 + 2 * (tile - t_begin));
     nxt = tile + 1;
     if (nxt < t_end) {                           // next tile's loads fly under this tile's MFMA phase
       const int row0_ = nxt * TR;
@@ -1180,7 +1266,9 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
         acc[tap] = v;
       }
     }
+    STAMP(st_on && tile - t_begin < 16, 19 + 2 * (tile - t_begin));
   }
+  STAMP(st_on, 50);
   // ---- results: C/D layout of the 16x16 MFMA: column (ci) = lane & 15, rows (co) = 4 (lane >> 4) + e ---------------------
   float* slab = slabs + (int64_t)bx * (NT * CIN * COUT);
   if (xb != 0) {
@@ -1218,6 +1306,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
       for (int e = 0; e < 4; e++)
         __builtin_nontemporal_store(acc[t][e], &slab[((int64_t)(bi * CB + cob * 16 + 4 * (lane >> 4) + e) * NT + t) * CIN + bj * CB + cib * 16 + (lane & 15)]);
   }
+  STAMP(st_on, 51);
 }
 
 template <int C, int WD, int PT, int XB = 0>
@@ -1243,10 +1332,16 @@ __global__ __launch_bounds__(256) void wgrad3x3_nhwc_kernel(const float* __restr
                                BnLazy{nullptr, nullptr, nullptr, nullptr}, xlev);
 }
 
-// Backward of one convolution in ONE launch: the first n_wg workgroups take the filter-gradient role (the longer one, so
-// it starts first), the rest the data-gradient role; the two are independent and fill the chip together.
+// Backward of one convolution in ONE launch: the first n_wg workgroups take the filter-gradient role, the rest the data-gradient
+// role; the two are independent and fill the chip together.  The whole grid must be resident at once: at C = 16 that is one
+// filter-gradient workgroup beside two data-gradient tiles per CU (256 + 512 workgroups), i.e. three waves per SIMD and at most
+// 168 registers - hence the waves-per-EU bound, which makes the compiler fold the accumulators into the vector registers (without
+// it: 162 VGPRs + 36 AGPRs, two workgroups per CU, and the last 256 data-gradient tiles start when earlier ones leave, 10 us into
+// a 20 us launch).  C = 32 / 64: 256 + 256 workgroups, two per CU.  (Measured, NOTES.md: at C = 16 the two roles end together once
+// the grid is resident, at C = 32 / 64 the data-gradient role ends last.)
 template <int C, int WD, int PTD, int PTW, int XB>
-__global__ __launch_bounds__(256) void conv3x3_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 16 ? 3 : 2, C == 16 ? 3 : 8)))
+void conv3x3_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           const float* __restrict__ w, float* __restrict__ dx,
                                                           float* __restrict__ slabs, int H, int total_rows, float nlev,
                                                           int n_tiles_w, int splits, int nblk2,
@@ -1256,6 +1351,7 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_kernel(const float* __restric
   static_assert(kBytesD >= 4096 || kBytesW >= 4096, "the filler role's 4 KB");
   __shared__ __attribute__((aligned(16))) unsigned char lds[kBytesD > kBytesW ? kBytesD : kBytesW];
   const int n_wg = splits * nblk2;
+  BSTAMP(0);
   if ((int)blockIdx.x < n_wg) {
     wgrad3x3_body<C, WD, PTW, XB>(x, dy, slabs, H, n_tiles_w, reinterpret_cast<float*>(lds), blockIdx.x % splits, splits,
                                   blockIdx.x / splits, lazy, xlev);
@@ -1277,6 +1373,7 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_kernel(const float* __restric
     }
     conv3x3_body<C, WD, PTD, true>(dy, w, dx, H, total_rows, nlev, reinterpret_cast<__bf16*>(lds), m, add, nullptr, 0, lazy);
   }
+  BSTAMP(1);
 }
 
 // Backward of a transition block's two stride-2 convolutions (3x3 `conv0` and the 1x1 shortcut, same input x) in ONE
@@ -1763,5 +1860,14 @@ int alignq_conv_stem_nhwc_wgrad(const float* x, const float* dy, float* dw, void
   e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
+
+#ifdef ALIGNQ_STAMPS
+int alignq_debug_read_conv_stamps(unsigned long long* host_out) {
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_conv_stamps), sizeof(unsigned long long) * 64);
+}
+int alignq_debug_read_conv_block_stamps(unsigned long long* host_out) {
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_conv_blk), sizeof(unsigned long long) * 2 * 4096);
+}
+#endif
 
 }  // extern "C"
