@@ -194,6 +194,7 @@ SIGNATURES = {
     "alignq_bnq_eval_fwd": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "alignq_eval_metrics": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "alignq_data_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _c.c_uint64, _i, _i, _vp, _i, _vp, _vp]),
+    "alignq_data_crop_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _c.c_uint64, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

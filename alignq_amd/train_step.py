@@ -232,13 +232,20 @@ class _CapturedStep:
         p = self._producer
         if p is None or self._graph is None:
             raise RuntimeError(f"{type(self).__name__}.next: needs set_producer(loader) and capture(...) first")
-        rows = p.next_batch_size()
-        if rows == 0:
+        rows = self._coming_rows(p)
+        if rows[0] == 0:
             raise RuntimeError(f"{type(self).__name__}.next: the loader's epoch is exhausted; call loader.begin_epoch")
-        if rows != self._static[0].shape[0]:
+        if rows != self._captured_rows():
             return self._eager_fallback(*p.next_batch())
-        p.skip(rows)
+        p.skip(*rows)
         return self._replay()
+
+    def _coming_rows(self, producer):
+        """Rows of the producer's coming batch(es), and `_captured_rows`: the rows the graph was captured with."""
+        return (producer.next_batch_size(),)
+
+    def _captured_rows(self):
+        return (self._static[0].shape[0],)
 
     def _record_inputs(self, static):
         """Inside a capture, in front of the iteration: the producer's batch launch into the graph's input buffers."""
@@ -610,9 +617,20 @@ class OfficeTrainStep(_CapturedStep):
             self.alpha = alpha
         return super().__call__(xs, ys, xt)
 
-    def set_producer(self, loader):
-        raise NotImplementedError("the Office steps (224 x 224 inputs decoded from JPEG files) take their batches from the caller; "
-                                  "alignq_amd.data covers the 32 x 32 byte-image sets")
+    def set_producer(self, pair):
+        """Attach alignq_amd.data.PairLoader (None detaches): the next `capture` records `pair.record(xs, ys, xt)` - the source
+        batch's launch and the target batch's, each moving its loader's cursor on - in front of the iteration, and `next()`
+        replays when both coming batches have the captured sizes (otherwise: filled eagerly, the eager fallback).  Without a
+        producer every graph is node for node what it was.  An existing capture is dropped."""
+        if pair is not None and not (hasattr(pair, "record") and hasattr(pair, "next_batch_sizes")):
+            raise TypeError("set_producer: the Office steps expect a data.PairLoader (a source and a target DeviceLoader)")
+        return super().set_producer(pair)
+
+    def _coming_rows(self, producer):
+        return tuple(producer.next_batch_sizes())
+
+    def _captured_rows(self):
+        return (self._static[0].shape[0], self._static[2].shape[0])
 
     def _backbone(self):
         """The ResNet feature extractor (DANN: `feature`)."""

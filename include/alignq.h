@@ -797,6 +797,31 @@ int alignq_eval_metrics(const float* logits, const int64_t* target, int B, int K
 int alignq_data_batch(const uint8_t* images, const int64_t* labels, const int64_t* perm, int32_t* cursor, int advance, const float* lut,
                       int64_t N, int B, int rank, int world, uint64_t seed, int pad, int flip, float* x_out, int nhwc, int64_t* y_out,
                       void* stream);
+/* alignq_data_crop_batch: the Office loaders (cdf_alignment_admm/dann_office/data/office.py:13-38, the same in dsan_office:
+ *   Resize((256, 256)), RandomCrop(224), RandomHorizontalFlip(), ToTensor(), Normalize(ImageNet mean, std); the test loader:
+ *   Resize, CenterCrop-style window, ToTensor, Normalize).  The resize is deterministic and is done once when the set is loaded.
+ *   images [N][side][side][3] bytes (HWC), labels, perm, cursor, advance, lut, rank / world, seed: as alignq_data_batch, including
+ *   the cursor protocol (cursor[2] counts the workgroups; the last one sets cursor[1] += advance and leaves cursor[2] at 0) and
+ *   the rule that a row with pos = cursor[1] + rank * B + i outside [0, N), or with s = perm[pos] outside [0, N), is NOT written:
+ *   neither x_out nor y_out.
+ *   Random draws: r = mix64(key + 0x9E3779B97F4A7C15 * (pos + 1)), key = mix64(mix64(seed) + epoch), exactly as above (uint64,
+ *   modulo 2^64; epoch = cursor[0] as uint32).  Then
+ *       dy = ((r & 0xFFFFFF) * span) >> 24;    dx = (((r >> 24) & 0xFFFFFF) * span) >> 24;    f = (r >> 48) & 1 if flip else 0
+ *   so dy, dx are in 0..span-1.  The window starts at row oy = off0 + dy and column ox = off0 + dx of the stored image:
+ *       output pixel (c, h, w), 0 <= h, w < crop, reads byte images[s][oy + h][ox + w'][c], w' = crop - 1 - w if f else w
+ *   (crop first, then mirror the cropped window: torchvision's order) and is lut[c][byte].  The window always lies inside the image
+ *   (the argument checks below): there is no padding.
+ *   Training: span = side - crop + 1, off0 = 0 (RandomCrop.get_params: a uniform integer in [0, side - crop] per axis).
+ *   Evaluation: span = 1, off0 = int(round((side - crop) / 2.0)) as CenterCrop computes it (16 for 256 -> 224); dy = dx = 0.
+ *   x_out: [B, 3, crop, crop] fp32, contiguous (nhwc = 0) or the same shape in channels-last storage (nhwc = 1); y_out[i] = labels[s],
+ *   written once per image.
+ *   ALIGNQ_EINVAL, before anything touches a device: a null pointer (perm may be NULL); lut or x_out not 16-byte aligned, labels /
+ *   perm / y_out not 8-byte aligned, cursor not 4-byte aligned; crop % 4 != 0, crop < 4, crop > side, side > 1024; span < 1,
+ *   span > 255; off0 < 0, off0 + span - 1 > side - crop; flip / nhwc not in {0, 1}; N < 1, B < 1, world < 1, rank outside
+ *   [0, world), advance < 0.  N <= 2^30, B <= 65535, advance <= 2^30 (ALIGNQ_EUNSUPPORTED above).                                  */
+int alignq_data_crop_batch(const uint8_t* images, const int64_t* labels, const int64_t* perm, int32_t* cursor, int advance,
+                           const float* lut, int64_t N, int side, int crop, int span, int off0, int B, int rank, int world,
+                           uint64_t seed, int flip, float* x_out, int nhwc, int64_t* y_out, void* stream);
 
 #ifdef __cplusplus
 }
