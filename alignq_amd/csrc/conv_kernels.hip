@@ -162,7 +162,10 @@ struct ConvLds {
   static constexpr int kBf16 = 3 * ((PT / WD) + 2) * (WD + 2) * conv_cp<C>();      // three bf16 images of the tile with halo
 };
 
-template <int C, int WD, int PT, bool DGRAD, int XB = 0>
+// IMG: `w` is not the fp32 filter but its pre-packed bf16 image, written by the weight quantiser's launch
+// (multi_tensor_kernels.hip, DESIGN.md "Filter images"): F[C/16][NS][64][8] for the forward, D (k = (8 - tap, co)) for the
+// data gradient - the very values the fp32 branch forms, one 16-byte load per k step and lane, no rintf and no conversion.
+template <int C, int WD, int PT, bool DGRAD, int XB = 0, bool IMG = false>
 __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const float* __restrict__ w,
                                              float* __restrict__ y, int H, int total_rows, float nlev, __bf16* lds,
                                              int block, const float* __restrict__ add,
@@ -270,22 +273,28 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
     //      loads on clamped addresses (a k step past the ninth tap reads tap 8 and is zeroed).  Requesting them together with the
     //      tile or ahead of it was measured and brings nothing (NOTES.md): issuing them takes 0.5 - 3 us, they are bound by their
     //      volume per workgroup, not by latency, and ahead of the tile they delay it (the memory counter returns in order).
+    if constexpr (IMG) {
+      const bf16x8* __restrict__ wi = reinterpret_cast<const bf16x8*>(w) + (cog * NS) * 64 + lane;
 #pragma unroll
-    for (int s = 0; s < NS; s++) {
-      const int k0 = 32 * s + 8 * q;
-      const bool live = k0 / C < 9;
-      const int tap = live ? k0 / C : 8, c0 = k0 % C;
-      float wr[8];
-      if (!DGRAD) {          // forward: W[co][tap][ci], 8 consecutive ci
-        const float* p = w + ((int64_t)(cog * 16 + m) * 9 + tap) * C + c0;
-        const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
-        wr[0] = a4.x; wr[1] = a4.y; wr[2] = a4.z; wr[3] = a4.w; wr[4] = b4.x; wr[5] = b4.y; wr[6] = b4.z; wr[7] = b4.w;
-      } else {               // data gradient: A[m = ci][k = (tap', co)] = W[co][8 - tap'][ci]
+      for (int s = 0; s < NS; s++) ab[s] = wi[s * 64];
+    } else {
 #pragma unroll
-        for (int j = 0; j < 8; j++) wr[j] = w[((int64_t)(c0 + j) * 9 + (8 - tap)) * C + cog * 16 + m];
+      for (int s = 0; s < NS; s++) {
+        const int k0 = 32 * s + 8 * q;
+        const bool live = k0 / C < 9;
+        const int tap = live ? k0 / C : 8, c0 = k0 % C;
+        float wr[8];
+        if (!DGRAD) {          // forward: W[co][tap][ci], 8 consecutive ci
+          const float* p = w + ((int64_t)(cog * 16 + m) * 9 + tap) * C + c0;
+          const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
+          wr[0] = a4.x; wr[1] = a4.y; wr[2] = a4.z; wr[3] = a4.w; wr[4] = b4.x; wr[5] = b4.y; wr[6] = b4.z; wr[7] = b4.w;
+        } else {               // data gradient: A[m = ci][k = (tap', co)] = W[co][8 - tap'][ci]
+#pragma unroll
+          for (int j = 0; j < 8; j++) wr[j] = w[((int64_t)(c0 + j) * 9 + (8 - tap)) * C + cog * 16 + m];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
       }
-#pragma unroll
-      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
     }
     STAMP(block == 0, SB + 3);
   }
@@ -401,14 +410,14 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
   STAMP(block == 0, SB + 5);
 }
 
-template <int C, int WD, int PT, bool DGRAD, int XB = 0>
+template <int C, int WD, int PT, bool DGRAD, int XB = 0, bool IMG = false>
 __global__ __launch_bounds__(256) void conv3x3_nhwc_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            float* __restrict__ y, int H, int total_rows, float nlev,
                                                            const float* __restrict__ add, float* __restrict__ bn_part,
                                                            float xlev) {
   __shared__ __attribute__((aligned(16))) __bf16 lds[ConvLds<C, WD, PT>::kBf16];
-  conv3x3_body<C, WD, PT, DGRAD, XB>(x, w, y, H, total_rows, nlev, lds, blockIdx.x, add, bn_part, gridDim.x,
-                                     BnLazy{nullptr, nullptr, nullptr, nullptr}, xlev);
+  conv3x3_body<C, WD, PT, DGRAD, XB, IMG>(x, w, y, H, total_rows, nlev, lds, blockIdx.x, add, bn_part, gridDim.x,
+                                          BnLazy{nullptr, nullptr, nullptr, nullptr}, xlev);
 }
 
 // ---- forward of the remaining Conv2d_Q shapes of the ResNet body: stride 2 (3x3, padding 1) and the 1x1 stride-2 shortcut
@@ -426,7 +435,8 @@ struct ConvGen {
 };
 
 // block / n_wg: index and count of the workgroups of THIS convolution (a launch may carry several roles)
-template <int CIN, int COUT, int WDI, int KS, int S, int PT>
+// IMG: `w` is the filter's forward image F[COUT/16][NS][64][8] (see conv3x3_body)
+template <int CIN, int COUT, int WDI, int KS, int S, int PT, bool IMG = false>
 __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, const float* __restrict__ w,
                                                  float* __restrict__ y, int H, int total_rows, float nlev,
                                                  float* __restrict__ bn_part, __bf16* lds, int block, int n_wg) {
@@ -481,16 +491,22 @@ __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, co
         *reinterpret_cast<bf16x4*>(Xlo + o) = l4;
       }
     }
+    if constexpr (IMG) {
+      const bf16x8* __restrict__ wi = reinterpret_cast<const bf16x8*>(w) + (cog * NS) * 64 + lane;
 #pragma unroll
-    for (int s = 0; s < NS; s++) {             // filter fragments behind the staged tile (see conv3x3_body): unconditional, clamped
-      const int k0 = 32 * s + 8 * q;
-      const bool live = k0 / CIN < KS * KS;
-      const int tap = live ? k0 / CIN : KS * KS - 1, c0 = k0 % CIN;
-      const float* p = w + ((int64_t)(cog * 16 + m) * (KS * KS) + tap) * CIN + c0;
-      const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
-      const float wr[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
+      for (int s = 0; s < NS; s++) ab[s] = wi[s * 64];
+    } else {
 #pragma unroll
-      for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
+      for (int s = 0; s < NS; s++) {             // filter fragments behind the staged tile (see conv3x3_body): unconditional, clamped
+        const int k0 = 32 * s + 8 * q;
+        const bool live = k0 / CIN < KS * KS;
+        const int tap = live ? k0 / CIN : KS * KS - 1, c0 = k0 % CIN;
+        const float* p = w + ((int64_t)(cog * 16 + m) * (KS * KS) + tap) * CIN + c0;
+        const float4 a4 = *reinterpret_cast<const float4*>(p), b4 = *reinterpret_cast<const float4*>(p + 4);
+        const float wr[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int j = 0; j < 8; j++) ab[s][j] = (__bf16)rintf((live ? wr[j] : 0.f) * nlev);
+      }
     }
   }
   __syncthreads();
@@ -584,17 +600,17 @@ __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, co
   }
 }
 
-template <int CIN, int COUT, int WDI, int KS, int S, int PT>
+template <int CIN, int COUT, int WDI, int KS, int S, int PT, bool IMG = false>
 __global__ __launch_bounds__(256) void convgen_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           float* __restrict__ y, int H, int total_rows, float nlev,
                                                           float* __restrict__ bn_part) {
   __shared__ __attribute__((aligned(16))) __bf16 lds[3 * ConvGen<CIN, COUT, WDI, KS, S, PT>::ARR];
-  convgen_fwd_body<CIN, COUT, WDI, KS, S, PT>(x, w, y, H, total_rows, nlev, bn_part, lds, blockIdx.x, gridDim.x);
+  convgen_fwd_body<CIN, COUT, WDI, KS, S, PT, IMG>(x, w, y, H, total_rows, nlev, bn_part, lds, blockIdx.x, gridDim.x);
 }
 
 // Both convolutions of a transition block (3x3 and 1x1, stride 2, same input) in ONE launch: the first n3 workgroups take
 // the 3x3 role, the rest the 1x1 role (a launch boundary costs more than the 1x1 convolution itself).
-template <int CIN, int COUT, int WDI, int PT3, int PT1>
+template <int CIN, int COUT, int WDI, int PT3, int PT1, bool IMG = false>
 __global__ __launch_bounds__(256) void transition_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w3,
                                                              const float* __restrict__ w1, float* __restrict__ y3,
                                                              float* __restrict__ y1, int H, int total_rows, float nlev,
@@ -602,10 +618,10 @@ __global__ __launch_bounds__(256) void transition_fwd_kernel(const float* __rest
   constexpr int A3 = ConvGen<CIN, COUT, WDI, 3, 2, PT3>::ARR, A1 = ConvGen<CIN, COUT, WDI, 1, 2, PT1>::ARR;
   __shared__ __attribute__((aligned(16))) __bf16 lds[3 * (A3 > A1 ? A3 : A1)];
   if ((int)blockIdx.x < n3)
-    convgen_fwd_body<CIN, COUT, WDI, 3, 2, PT3>(x, w3, y3, H, total_rows, nlev, part3, lds, blockIdx.x, n3);
+    convgen_fwd_body<CIN, COUT, WDI, 3, 2, PT3, IMG>(x, w3, y3, H, total_rows, nlev, part3, lds, blockIdx.x, n3);
   else
-    convgen_fwd_body<CIN, COUT, WDI, 1, 2, PT1>(x, w1, y1, H, total_rows, nlev, part1, lds, blockIdx.x - n3,
-                                                (int)gridDim.x - n3);
+    convgen_fwd_body<CIN, COUT, WDI, 1, 2, PT1, IMG>(x, w1, y1, H, total_rows, nlev, part1, lds, blockIdx.x - n3,
+                                                     (int)gridDim.x - n3);
 }
 
 // ---- data gradient of the stride-2 transition convolutions -----------------------------------------------------------
@@ -617,7 +633,9 @@ __global__ __launch_bounds__(256) void transition_fwd_kernel(const float* __rest
 // WITH1 (KS == 3): the data gradient of the block's 1x1 stride-2 shortcut convolution (same input, own output gradient dy1,
 // filter w1 and lazy batch-norm record) is accumulated in the same pass as a tenth tap (it reaches input pixel (2i, 2j) only,
 // from dy1 pixel (i, j)): its output pixels sit behind the 3x3 image in the LDS arrays.
-template <int CIN, int COUT, int WDI, int KS, int PT, bool WITH1>
+// IMG: `w` (and `w1`) are the filters' data-gradient images D[CIN/16][NSD][64][8] with the taps in this kernel's own order (flip = 0);
+// the 1x1 shortcut's image supplies the k steps behind the 3x3's (tap 9 starts on a step boundary: 9 * COUT % 32 == 0).
+template <int CIN, int COUT, int WDI, int KS, int PT, bool WITH1, bool IMG = false>
 __device__ __forceinline__ void dgrad_s2_body(const float* __restrict__ dy, const float* __restrict__ w,
                                               float* __restrict__ dx, int H, int total_rows, float nlev,
                                               const float* __restrict__ add, BnLazy lazy, __bf16* lds, int block,
@@ -742,16 +760,29 @@ __device__ __forceinline__ void dgrad_s2_body(const float* __restrict__ dy, cons
   const int cig = wv % NCG, pp = wv / NCG;
   const int m = lane & 15, q = lane >> 4;
   bf16x8 ab[NS];
+  if constexpr (IMG) {
+    static_assert((KS * KS * COUT) % 32 == 0 && COUT % 32 == 0, "whole k steps per filter");
+    constexpr int NS3 = KS * KS * COUT / 32;      // k steps of `w`'s image; the rest (WITH1) are the 1x1 filter's
+    const bf16x8* __restrict__ wi = reinterpret_cast<const bf16x8*>(w) + (cig * NS3) * 64 + lane;
 #pragma unroll
-  for (int s = 0; s < NS; s++) {
-    const int k0 = 32 * s + 8 * q;
-    const int tap = k0 / COUT, c0 = k0 % COUT;
+    for (int s = 0; s < NS3; s++) ab[s] = wi[s * 64];
+    if constexpr (WITH1) {
+      const bf16x8* __restrict__ wj = reinterpret_cast<const bf16x8*>(w1) + (cig * (NS - NS3)) * 64 + lane;
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float v = 0.f;
-      if (tap < KS * KS) v = w[((int64_t)(c0 + j) * (KS * KS) + tap) * CIN + cig * 16 + m];
-      else if (WITH1 && tap == KS * KS) v = w1[(int64_t)(c0 + j) * CIN + cig * 16 + m];
-      ab[s][j] = (__bf16)rintf(v * nlev);
+      for (int s = NS3; s < NS; s++) ab[s] = wj[(s - NS3) * 64];
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      const int k0 = 32 * s + 8 * q;
+      const int tap = k0 / COUT, c0 = k0 % COUT;
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        float v = 0.f;
+        if (tap < KS * KS) v = w[((int64_t)(c0 + j) * (KS * KS) + tap) * CIN + cig * 16 + m];
+        else if (WITH1 && tap == KS * KS) v = w1[(int64_t)(c0 + j) * CIN + cig * 16 + m];
+        ab[s][j] = (__bf16)rintf(v * nlev);
+      }
     }
   }
   __syncthreads();
@@ -798,23 +829,27 @@ struct DgradS2Lds {
   static constexpr int kBf16 = 3 * (((TR / 2 + P) * (WDI / 2 + P) + 1) + (WITH1 ? (TR / 2) * (WDI / 2) : 0)) * (COUT + 8);
 };
 
-template <int CIN, int COUT, int WDI, int KS, int PT>
+template <int CIN, int COUT, int WDI, int KS, int PT, bool IMG = false>
 __global__ __launch_bounds__(256) void dgrad_s2_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                        float* __restrict__ dx, int H, int total_rows, float nlev,
                                                        const float* __restrict__ add, BnLazy lazy) {
   __shared__ __attribute__((aligned(16))) __bf16 lds[DgradS2Lds<CIN, COUT, WDI, KS, PT, false>::kBf16];
-  dgrad_s2_body<CIN, COUT, WDI, KS, PT, false>(dy, w, dx, H, total_rows, nlev, add, lazy, lds, blockIdx.x);
+  dgrad_s2_body<CIN, COUT, WDI, KS, PT, false, IMG>(dy, w, dx, H, total_rows, nlev, add, lazy, lds, blockIdx.x);
 }
 
 template <int CIN, int COUT, int WDI, int KS, int PT>
 int launch_dgrad_s2(const float* dy, const float* w, float* dx, int B, int H, float nlev, const float* add, BnLazy lazy,
-                    hipStream_t st) {
+                    hipStream_t st, bool img = false) {
   constexpr int TR = PT / WDI;
   static_assert(TR % 2 == 0, "even number of input rows per tile");
   if (H % TR) return ALIGNQ_EUNSUPPORTED;
   const int total_rows = B * H;
-  hipLaunchKernelGGL((dgrad_s2_kernel<CIN, COUT, WDI, KS, PT>), total_rows / TR, 256, 0, st, dy, w, dx, H, total_rows, nlev,
-                     add, lazy);
+  if (img)
+    hipLaunchKernelGGL((dgrad_s2_kernel<CIN, COUT, WDI, KS, PT, true>), total_rows / TR, 256, 0, st, dy, w, dx, H, total_rows, nlev,
+                       add, lazy);
+  else
+    hipLaunchKernelGGL((dgrad_s2_kernel<CIN, COUT, WDI, KS, PT>), total_rows / TR, 256, 0, st, dy, w, dx, H, total_rows, nlev,
+                       add, lazy);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -1029,24 +1064,34 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 }
 
 template <int CIN, int COUT, int WDI, int KS, int S, int PT>
-int launch_gen(const float* x, const float* w, float* y, int B, int H, float nlev, float* bn_part, hipStream_t st) {
+int launch_gen(const float* x, const float* w, float* y, int B, int H, float nlev, float* bn_part, hipStream_t st,
+               bool img = false) {
   constexpr int TR = ConvGen<CIN, COUT, WDI, KS, S, PT>::TR;
   if (H % TR) return ALIGNQ_EUNSUPPORTED;
   const int total_rows = B * H;
-  hipLaunchKernelGGL((convgen_fwd_kernel<CIN, COUT, WDI, KS, S, PT>), total_rows / TR, 256, 0, st, x, w, y, H, total_rows,
-                     nlev, bn_part);
+  if (img)
+    hipLaunchKernelGGL((convgen_fwd_kernel<CIN, COUT, WDI, KS, S, PT, true>), total_rows / TR, 256, 0, st, x, w, y, H, total_rows,
+                       nlev, bn_part);
+  else
+    hipLaunchKernelGGL((convgen_fwd_kernel<CIN, COUT, WDI, KS, S, PT>), total_rows / TR, 256, 0, st, x, w, y, H, total_rows,
+                       nlev, bn_part);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
 
 template <int C, int WD, int PT>
 int launch(const float* x, const float* w, float* y, int B, int H, int dgrad, float nlev, const float* add, float* bn_part,
-           hipStream_t st, int xb = 0, float xlev = 1.0f) {
+           hipStream_t st, int xb = 0, float xlev = 1.0f, bool img = false) {
   constexpr int TR = PT / WD;
   const int total_rows = B * H;
   if (H % TR) return ALIGNQ_EUNSUPPORTED;
   const int grid = total_rows / TR;
-  if (dgrad) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, true, 0>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, nullptr, 1.0f);
+  if (img) {       // w: the forward / data-gradient filter image
+    if (dgrad) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, true, 0, true>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, nullptr, 1.0f);
+    else if (xb == 2) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 2, true>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
+    else if (xb == 1) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 1, true>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
+    else hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 0, true>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
+  } else if (dgrad) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, true, 0>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, nullptr, 1.0f);
   else if (xb == 2) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 2>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
   else if (xb == 1) hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 1>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
   else hipLaunchKernelGGL((conv3x3_nhwc_kernel<C, WD, PT, false, 0>), grid, 256, 0, st, x, w, y, H, total_rows, nlev, add, bn_part, xlev);
@@ -1339,7 +1384,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_nhwc_kernel(const float* __restr
 // it: 162 VGPRs + 36 AGPRs, two workgroups per CU, and the last 256 data-gradient tiles start when earlier ones leave, 10 us into
 // a 20 us launch).  C = 32 / 64: 256 + 256 workgroups, two per CU.  (Measured, NOTES.md: at C = 16 the two roles end together once
 // the grid is resident, at C = 32 / 64 the data-gradient role ends last.)
-template <int C, int WD, int PTD, int PTW, int XB>
+template <int C, int WD, int PTD, int PTW, int XB, bool IMG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 16 ? 3 : 2, C == 16 ? 3 : 8)))
 void conv3x3_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           const float* __restrict__ w, float* __restrict__ dx,
@@ -1371,7 +1416,7 @@ void conv3x3_bwd_kernel(const float* __restrict__ x, const float* __restrict__ d
       const int i = (m / (8 * dg_R)) * 8 + (m & 7), r = (m >> 3) % dg_R;
       m = dg_R * i + r;
     }
-    conv3x3_body<C, WD, PTD, true>(dy, w, dx, H, total_rows, nlev, reinterpret_cast<__bf16*>(lds), m, add, nullptr, 0, lazy);
+    conv3x3_body<C, WD, PTD, true, 0, IMG>(dy, w, dx, H, total_rows, nlev, reinterpret_cast<__bf16*>(lds), m, add, nullptr, 0, lazy);
   }
   BSTAMP(1);
 }
@@ -1380,7 +1425,7 @@ void conv3x3_bwd_kernel(const float* __restrict__ x, const float* __restrict__ d
 // launch instead of four: workgroups [0, n_d) form the data gradient of BOTH convolutions (dgrad_s2_body<.., WITH1>; the longest
 // role, so it is dispatched first), the next n_w3 the 3x3 filter gradient's partial slabs, the rest the 1x1 filter gradient's.
 // The roles are independent.
-template <int CIN, int COUT, int WDI, int PTW3, int PTW1, int PTD>
+template <int CIN, int COUT, int WDI, int PTW3, int PTW1, int PTD, bool IMG = false>
 __global__ __launch_bounds__(256) void transition_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy3,
                                                              const float* __restrict__ dy1, const float* __restrict__ w3,
                                                              const float* __restrict__ w1, float* __restrict__ dx,
@@ -1404,8 +1449,8 @@ __global__ __launch_bounds__(256) void transition_bwd_kernel(const float* __rest
       const int i = (m / (8 * dg_R)) * 8 + (m & 7), r = (m >> 3) % dg_R;
       m = dg_R * i + r;
     }
-    dgrad_s2_body<CIN, COUT, WDI, 3, PTD, true>(dy3, w3, dx, 2 * Ho, 0x7fffffff, nlev, add, lazy3,
-                                                reinterpret_cast<__bf16*>(lds), m, dy1, w1, lazy1);
+    dgrad_s2_body<CIN, COUT, WDI, 3, PTD, true, IMG>(dy3, w3, dx, 2 * Ho, 0x7fffffff, nlev, add, lazy3,
+                                                     reinterpret_cast<__bf16*>(lds), m, dy1, w1, lazy1);
   } else if (b < n_d + n_w3) {
     const int c = b - n_d;
     wgrad_body<CIN, COUT, WDI, 3, 2, PTW3>(x, dy3, slabs3, Ho, n_tiles3, reinterpret_cast<float*>(lds), c % splits3, splits3,
@@ -1464,7 +1509,8 @@ int launch_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, i
 
 template <int C, int WD, int PTD, int PTW>
 int launch_bwd(const float* x, const float* dy, const float* w, float* dx, float* ws, int B, int H, float nlev,
-               int* n_slabs_out, const float* add, BnLazy lazy, hipStream_t st, int xb, float xlev, const RedFill& fill) {
+               int* n_slabs_out, const float* add, BnLazy lazy, hipStream_t st, int xb, float xlev, const RedFill& fill,
+               bool img) {
   constexpr int TRD = PTD / WD, TRW = PTW / WD;
   if (H % TRD || H % TRW) return ALIGNQ_EUNSUPPORTED;
   const int total_rows = B * H;
@@ -1481,8 +1527,10 @@ int launch_bwd(const float* x, const float* dy, const float* w, float* dx, float
     const int R = per * TRW / TRD;
     if (R >= 1 && R * splits == n_d) dg_R = R;
   }
-#define LBW(XBV) hipLaunchKernelGGL((conv3x3_bwd_kernel<C, WD, PTD, PTW, XBV>), grid, 256, 0, st, x, dy, w, dx, ws, H, total_rows, nlev, n_tiles_w, splits, NB * NB, add, lazy, xlev, dg_R, fill, n_d)
-  if (xb == 2) LBW(2); else if (xb == 1) LBW(1); else LBW(0);
+#define LBW(XBV, IM) hipLaunchKernelGGL((conv3x3_bwd_kernel<C, WD, PTD, PTW, XBV, IM>), grid, 256, 0, st, x, dy, w, dx, ws, H, total_rows, nlev, n_tiles_w, splits, NB * NB, add, lazy, xlev, dg_R, fill, n_d)
+  if (img) {       // w: the data-gradient filter image
+    if (xb == 2) LBW(2, true); else if (xb == 1) LBW(1, true); else LBW(0, true);
+  } else if (xb == 2) LBW(2, false); else if (xb == 1) LBW(1, false); else LBW(0, false);
 #undef LBW
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -1511,12 +1559,16 @@ int launch_wgradgen(const float* x, const float* dy, float* dw, float* ws, int B
 
 template <int CIN, int COUT, int WDI, int PT3, int PT1>
 int launch_transition_fwd(const float* x, const float* w3, const float* w1, float* y3, float* y1, int B, int H, float nlev,
-                          float* part3, float* part1, hipStream_t st) {
+                          float* part3, float* part1, hipStream_t st, bool img) {
   constexpr int TR3 = ConvGen<CIN, COUT, WDI, 3, 2, PT3>::TR, TR1 = ConvGen<CIN, COUT, WDI, 1, 2, PT1>::TR;
   if (H % TR3 || H % TR1) return ALIGNQ_EUNSUPPORTED;
   const int total_rows = B * H, n3 = total_rows / TR3, n1 = total_rows / TR1;
-  hipLaunchKernelGGL((transition_fwd_kernel<CIN, COUT, WDI, PT3, PT1>), n3 + n1, 256, 0, st, x, w3, w1, y3, y1, H, total_rows,
-                     nlev, part3, part1, n3);
+  if (img)
+    hipLaunchKernelGGL((transition_fwd_kernel<CIN, COUT, WDI, PT3, PT1, true>), n3 + n1, 256, 0, st, x, w3, w1, y3, y1, H,
+                       total_rows, nlev, part3, part1, n3);
+  else
+    hipLaunchKernelGGL((transition_fwd_kernel<CIN, COUT, WDI, PT3, PT1>), n3 + n1, 256, 0, st, x, w3, w1, y3, y1, H, total_rows,
+                       nlev, part3, part1, n3);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -1524,7 +1576,7 @@ int launch_transition_fwd(const float* x, const float* w3, const float* w1, floa
 template <int CIN, int COUT, int WDI, int PTW3, int PTW1, int PTD>
 int launch_transition_bwd(const float* x, const float* dy3, const float* dy1, const float* w3, const float* w1, float* dx,
                           float* ws3, float* ws1, int B, int Ho, float nlev, int* ns3, int* ns1, const float* add,
-                          BnLazy lazy3, BnLazy lazy1, hipStream_t st) {
+                          BnLazy lazy3, BnLazy lazy1, hipStream_t st, bool img) {
   using G3 = WgradGeo<CIN, COUT, WDI, 3, 2, PTW3>;
   using G1 = WgradGeo<CIN, COUT, WDI, 1, 2, PTW1>;
   constexpr int TRD = PTD / WDI;
@@ -1546,9 +1598,14 @@ int launch_transition_bwd(const float* x, const float* dy3, const float* dy1, co
       if (R >= 1 && R * splits3 == n_d) dg_R = R;
     }
   }
-  hipLaunchKernelGGL((transition_bwd_kernel<CIN, COUT, WDI, PTW3, PTW1, PTD>), (splits3 + splits1) * NBY + n_d, 256, 0, st, x,
-                     dy3, dy1, w3, w1, dx, ws3, ws1, Ho, n_tiles3, n_tiles1, splits3, splits1, n_d, nlev, add, lazy3, lazy1,
-                     dg_R);
+  if (img)
+    hipLaunchKernelGGL((transition_bwd_kernel<CIN, COUT, WDI, PTW3, PTW1, PTD, true>), (splits3 + splits1) * NBY + n_d, 256, 0, st,
+                       x, dy3, dy1, w3, w1, dx, ws3, ws1, Ho, n_tiles3, n_tiles1, splits3, splits1, n_d, nlev, add, lazy3, lazy1,
+                       dg_R);
+  else
+    hipLaunchKernelGGL((transition_bwd_kernel<CIN, COUT, WDI, PTW3, PTW1, PTD>), (splits3 + splits1) * NBY + n_d, 256, 0, st, x,
+                       dy3, dy1, w3, w1, dx, ws3, ws1, Ho, n_tiles3, n_tiles1, splits3, splits1, n_d, nlev, add, lazy3, lazy1,
+                       dg_R);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   *ns3 = splits3;
@@ -1586,9 +1643,24 @@ static int act_bins_ok(const void* x_bins, int x_bin_bytes, int a_bit) {
   return (x_bin_bytes == 1 || x_bin_bytes == 2) && a_bit >= 1 && a_bit <= 16 && !(reinterpret_cast<uintptr_t>(x_bins) & 15);
 }
 
-int alignq_conv3x3_nhwc(const float* x, const float* wt, float* y, int B, int H, int W, int C, int w_bit, int dgrad,
-                        const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit, void* stream) {
+// the forward (dgrad = 0) or data-gradient (dgrad = 1) image inside a filter's image buffer (alignq_filter_image_bytes): F comes
+// first, (CO / 16) * ceil(KK * CI / 32) * 512 bf16 elements, D follows it.  nullptr stays nullptr.
+static const float* image_of(const void* w_img, int CO, int KK, int CI, int dgrad) {
+  if (!w_img) return nullptr;
+  const size_t f = (size_t)(CO / 16) * ((KK * CI + 31) / 32) * 512;
+  return reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(w_img) + (dgrad ? f : 0));
+}
+
+static int conv3x3_nhwc(const float* x, const float* wt, const void* w_img, float* y, int B, int H, int W, int C, int w_bit,
+                        int dgrad, const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit,
+                        void* stream) {
   if ((!x && !x_bins) || !wt || !y || B < 1 || H < 1) return ALIGNQ_EINVAL;
+  if (w_img) {       // the kernels read the image in place of the fp32 filter
+    if (C != 16 && C != 32 && C != 64) return ALIGNQ_EUNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(w_img) & 15) return ALIGNQ_EUNSUPPORTED;
+    wt = image_of(w_img, C, 9, C, dgrad);
+  }
+  const bool img = w_img != nullptr;
   if (x_bins && (dgrad || !act_bins_ok(x_bins, x_bin_bytes, a_bit))) return ALIGNQ_EINVAL;
   if (w_bit < 1 || w_bit > 8) return ALIGNQ_EUNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(y)) & 15) return ALIGNQ_EUNSUPPORTED;
@@ -1597,17 +1669,31 @@ int alignq_conv3x3_nhwc(const float* x, const float* wt, float* y, int B, int H,
   if (x_bins) {        // N2: the activation operand as int8 / int16 level indices of an a_bit-bit ADMM-formula quantiser
     const float xlev = (float)((1 << a_bit) - 1);
     const float* xb_ = reinterpret_cast<const float*>(x_bins);
-    if (C == 16 && W == 32) return launch<16, 32, 256>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev);
-    if (C == 32 && W == 16) return launch<32, 16, 128>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev);
-    if (C == 64 && W == 8) return launch<64, 8, 32>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev);
+    if (C == 16 && W == 32) return launch<16, 32, 256>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev, img);
+    if (C == 32 && W == 16) return launch<32, 16, 128>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev, img);
+    if (C == 64 && W == 8) return launch<64, 8, 32>(xb_, wt, y, B, H, 0, nlev, add, bn_part, st, x_bin_bytes, xlev, img);
     return ALIGNQ_EUNSUPPORTED;
   }
   // tile sizes measured on MI355X (forward us per layer at batch 128): C=16: 256 pixels 7.8 (128: 8.7); C=32: 128 pixels 8.0
   // (256: 11.0); C=64: 32 pixels 9.3 (64: 12.3)
-  if (C == 16 && W == 32) return launch<16, 32, 256>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st);
-  if (C == 32 && W == 16) return launch<32, 16, 128>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st);
-  if (C == 64 && W == 8) return launch<64, 8, 32>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st);
+  if (C == 16 && W == 32) return launch<16, 32, 256>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st, 0, 1.0f, img);
+  if (C == 32 && W == 16) return launch<32, 16, 128>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st, 0, 1.0f, img);
+  if (C == 64 && W == 8) return launch<64, 8, 32>(x, wt, y, B, H, dgrad, nlev, add, bn_part, st, 0, 1.0f, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+
+int alignq_conv3x3_nhwc(const float* x, const float* wt, float* y, int B, int H, int W, int C, int w_bit, int dgrad,
+                        const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit, void* stream) {
+  return conv3x3_nhwc(x, wt, nullptr, y, B, H, W, C, w_bit, dgrad, add, bn_part, x_bins, x_bin_bytes, a_bit, stream);
+}
+
+// alignq_conv3x3_nhwc reading the filter from its images (w_img: alignq_weight_quant_fwd_multi_img's buffer for (C, 9, C), flip = 1,
+// written from the same wt at the same w_bit).  Bit-identical results.
+int alignq_conv3x3_nhwc_img(const float* x, const float* wt, const void* w_img, float* y, int B, int H, int W, int C, int w_bit,
+                            int dgrad, const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit,
+                            void* stream) {
+  if (!w_img) return ALIGNQ_EINVAL;
+  return conv3x3_nhwc(x, wt, w_img, y, B, H, W, C, w_bit, dgrad, add, bn_part, x_bins, x_bin_bytes, a_bit, stream);
 }
 
 size_t alignq_conv3x3_wgrad_ws_bytes(int C) { return (size_t)256 * 9 * (size_t)C * C * sizeof(float); }
@@ -1656,8 +1742,9 @@ int alignq_conv3x3_wgrad_reduce_multi(int T, const void* const* ws, float* const
 
 // Both gradients of one convolution in a single launch (data gradient as alignq_conv3x3_nhwc(dgrad = 1), filter-gradient
 // partial sums as alignq_conv3x3_nhwc_wgrad with a deferred reduction: *n_slabs_out slabs are left in ws).
-int alignq_conv3x3_nhwc_bwd_fill(const float* x, const float* dy, const float* wt, float* dx, void* ws, int B, int H, int W,
-                                 int C, int w_bit, int* n_slabs_out, const float* add, const float* bn_z, const float* bn_ab,
+static int conv3x3_nhwc_bwd_fill(const float* x, const float* dy, const float* wt, const void* w_img, float* dx, void* ws, int B,
+                                 int H, int W, int C, int w_bit, int* n_slabs_out, const float* add, const float* bn_z,
+                                 const float* bn_ab,
                             const float* bn_save, const float* bn_ktot, const float* bn_dx_part, float* bn_dgamma,
                             float* bn_dbeta, const void* x_bins, int x_bin_bytes, int a_bit, int n_fill,
                                  const void* const* fill_ws, float* const* fill_dw, const int* fill_n_slabs,
@@ -1684,10 +1771,40 @@ int alignq_conv3x3_nhwc_bwd_fill(const float* x, const float* dy, const float* w
     fill.blk0[i + 1] = fill.blk0[i] + wgrad_reduce_blocks(fill_n_slabs[i], fill_n_elem[i], 256);
   }
   for (int i = n_fill; i < kFill; i++) fill.blk0[i + 1] = fill.blk0[i];
-  if (C == 16 && W == 32) return launch_bwd<16, 32, 256, 128>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill);
-  if (C == 32 && W == 16) return launch_bwd<32, 16, 128, 128>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill);
-  if (C == 64 && W == 8) return launch_bwd<64, 8, 32, 64>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill);
+  const bool img = w_img != nullptr;
+  if (img) {       // the data-gradient role reads the D image in place of the fp32 filter
+    if (C != 16 && C != 32 && C != 64) return ALIGNQ_EUNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(w_img) & 15) return ALIGNQ_EUNSUPPORTED;
+    wt = image_of(w_img, C, 9, C, 1);
+  }
+  if (C == 16 && W == 32) return launch_bwd<16, 32, 256, 128>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill, img);
+  if (C == 32 && W == 16) return launch_bwd<32, 16, 128, 128>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill, img);
+  if (C == 64 && W == 8) return launch_bwd<64, 8, 32, 64>(x, dy, wt, dx, (float*)ws, B, H, nlev, n_slabs_out, add, lazy, st, xb, xlev, fill, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+
+int alignq_conv3x3_nhwc_bwd_fill(const float* x, const float* dy, const float* wt, float* dx, void* ws, int B, int H, int W,
+                                 int C, int w_bit, int* n_slabs_out, const float* add, const float* bn_z, const float* bn_ab,
+                                 const float* bn_save, const float* bn_ktot, const float* bn_dx_part, float* bn_dgamma,
+                                 float* bn_dbeta, const void* x_bins, int x_bin_bytes, int a_bit, int n_fill,
+                                 const void* const* fill_ws, float* const* fill_dw, const int* fill_n_slabs,
+                                 const int* fill_n_elem, void* stream) {
+  return conv3x3_nhwc_bwd_fill(x, dy, wt, nullptr, dx, ws, B, H, W, C, w_bit, n_slabs_out, add, bn_z, bn_ab, bn_save, bn_ktot,
+                               bn_dx_part, bn_dgamma, bn_dbeta, x_bins, x_bin_bytes, a_bit, n_fill, fill_ws, fill_dw, fill_n_slabs,
+                               fill_n_elem, stream);
+}
+
+// alignq_conv3x3_nhwc_bwd_fill with the data-gradient role reading the filter's D image (w_img as in alignq_conv3x3_nhwc_img).
+int alignq_conv3x3_nhwc_bwd_fill_img(const float* x, const float* dy, const float* wt, const void* w_img, float* dx, void* ws,
+                                     int B, int H, int W, int C, int w_bit, int* n_slabs_out, const float* add,
+                                     const float* bn_z, const float* bn_ab, const float* bn_save, const float* bn_ktot,
+                                     const float* bn_dx_part, float* bn_dgamma, float* bn_dbeta, const void* x_bins,
+                                     int x_bin_bytes, int a_bit, int n_fill, const void* const* fill_ws, float* const* fill_dw,
+                                     const int* fill_n_slabs, const int* fill_n_elem, void* stream) {
+  if (!w_img) return ALIGNQ_EINVAL;
+  return conv3x3_nhwc_bwd_fill(x, dy, wt, w_img, dx, ws, B, H, W, C, w_bit, n_slabs_out, add, bn_z, bn_ab, bn_save, bn_ktot,
+                               bn_dx_part, bn_dgamma, bn_dbeta, x_bins, x_bin_bytes, a_bit, n_fill, fill_ws, fill_dw, fill_n_slabs,
+                               fill_n_elem, stream);
 }
 
 int alignq_conv3x3_nhwc_bwd(const float* x, const float* dy, const float* wt, float* dx, void* ws, int B, int H, int W,
@@ -1713,19 +1830,32 @@ int alignq_conv_gen_bn_parts(int B, int H_in, int W_in, int CIN, int COUT, int K
   if (!tr || B < 1 || H_in < 2 || (H_in % 2) || ((H_in / 2) % tr)) return 0;
   return B * (H_in / 2) / tr;
 }
-int alignq_conv_gen_nhwc_fwd(const float* x, const float* wt, float* y, int B, int H_in, int W_in, int CIN, int COUT, int KS,
-                             int stride, int w_bit, float* bn_part, void* stream) {
+static int conv_gen_nhwc_fwd(const float* x, const float* wt, const void* w_img, float* y, int B, int H_in, int W_in, int CIN,
+                             int COUT, int KS, int stride, int w_bit, float* bn_part, void* stream) {
   if (!x || !wt || !y || B < 1) return ALIGNQ_EINVAL;
+  if (reinterpret_cast<uintptr_t>(w_img) & 15) return ALIGNQ_EUNSUPPORTED;
+  const bool img = w_img != nullptr;
   if (w_bit < 1 || w_bit > 8 || !alignq_conv_gen_bn_parts(B, H_in, W_in, CIN, COUT, KS, stride)) return ALIGNQ_EUNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(y)) & 15) return ALIGNQ_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const float nlev = (float)((1 << w_bit) - 1);
   const int H = H_in / 2;
-  if (CIN == 16 && KS == 3) return launch_gen<16, 32, 32, 3, 2, 64>(x, wt, y, B, H, nlev, bn_part, st);
-  if (CIN == 16 && KS == 1) return launch_gen<16, 32, 32, 1, 2, 128>(x, wt, y, B, H, nlev, bn_part, st);
-  if (CIN == 32 && KS == 3) return launch_gen<32, 64, 16, 3, 2, 32>(x, wt, y, B, H, nlev, bn_part, st);
-  if (CIN == 32 && KS == 1) return launch_gen<32, 64, 16, 1, 2, 64>(x, wt, y, B, H, nlev, bn_part, st);
+  if (img) wt = image_of(w_img, COUT, KS * KS, CIN, 0);       // (the shape check above fixed COUT = 2 CIN, CIN in {16, 32})
+  if (CIN == 16 && KS == 3) return launch_gen<16, 32, 32, 3, 2, 64>(x, wt, y, B, H, nlev, bn_part, st, img);
+  if (CIN == 16 && KS == 1) return launch_gen<16, 32, 32, 1, 2, 128>(x, wt, y, B, H, nlev, bn_part, st, img);
+  if (CIN == 32 && KS == 3) return launch_gen<32, 64, 16, 3, 2, 32>(x, wt, y, B, H, nlev, bn_part, st, img);
+  if (CIN == 32 && KS == 1) return launch_gen<32, 64, 16, 1, 2, 64>(x, wt, y, B, H, nlev, bn_part, st, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+int alignq_conv_gen_nhwc_fwd(const float* x, const float* wt, float* y, int B, int H_in, int W_in, int CIN, int COUT, int KS,
+                             int stride, int w_bit, float* bn_part, void* stream) {
+  return conv_gen_nhwc_fwd(x, wt, nullptr, y, B, H_in, W_in, CIN, COUT, KS, stride, w_bit, bn_part, stream);
+}
+// the same reading the filter's forward image (w_img: alignq_weight_quant_fwd_multi_img's buffer for (COUT, KS*KS, CIN), flip = 0)
+int alignq_conv_gen_nhwc_fwd_img(const float* x, const float* wt, const void* w_img, float* y, int B, int H_in, int W_in, int CIN,
+                                 int COUT, int KS, int stride, int w_bit, float* bn_part, void* stream) {
+  if (!w_img) return ALIGNQ_EINVAL;
+  return conv_gen_nhwc_fwd(x, wt, w_img, y, B, H_in, W_in, CIN, COUT, KS, stride, w_bit, bn_part, stream);
 }
 
 // Filter gradient of the transition convolutions (shapes of alignq_conv_gen_nhwc_fwd): dW [COUT,KS,KS,CIN] from x [B,H_in,W_in,CIN]
@@ -1751,11 +1881,13 @@ int alignq_conv_gen_nhwc_wgrad(const float* x, const float* dy, float* dw, void*
 
 // Data gradient of the transition convolutions: dx [B,H_in,W_in,CIN] from dy [B,H_in/2,W_in/2,COUT]; bn_* as in
 // alignq_conv3x3_nhwc_bwd (dy given in the lazy batch-norm form when bn_z != NULL).
-int alignq_conv_gen_nhwc_dgrad(const float* dy, const float* wt, float* dx, int B, int H_in, int W_in, int CIN, int COUT, int KS,
-                               int stride, int w_bit, const float* add, const float* bn_z, const float* bn_ab,
+static int conv_gen_nhwc_dgrad(const float* dy, const float* wt, const void* w_img, float* dx, int B, int H_in, int W_in, int CIN,
+                               int COUT, int KS, int stride, int w_bit, const float* add, const float* bn_z, const float* bn_ab,
                                const float* bn_save, const float* bn_ktot, const float* bn_dx_part, float* bn_dgamma,
                                float* bn_dbeta, void* stream) {
   if (!dy || !wt || !dx || B < 1) return ALIGNQ_EINVAL;
+  if (reinterpret_cast<uintptr_t>(w_img) & 15) return ALIGNQ_EUNSUPPORTED;
+  const bool img = w_img != nullptr;
   if (add && (reinterpret_cast<uintptr_t>(add) & 15)) return ALIGNQ_EUNSUPPORTED;
   if (bn_z && (!bn_ab || !bn_save || (!bn_ktot && !bn_dx_part))) return ALIGNQ_EINVAL;
   if (w_bit < 1 || w_bit > 8 || !alignq_conv_gen_bn_parts(B, H_in, W_in, CIN, COUT, KS, stride)) return ALIGNQ_EUNSUPPORTED;
@@ -1764,19 +1896,39 @@ int alignq_conv_gen_nhwc_dgrad(const float* dy, const float* wt, float* dx, int 
   const float nlev = (float)((1 << w_bit) - 1);
   BnLazy lazy{bn_z, bn_ab, bn_save, bn_ktot};
   if (int rc = lazy_parts(lazy, bn_dx_part, bn_dgamma, bn_dbeta, B, COUT, (H_in / 2) * (W_in / 2))) return rc;
-  if (CIN == 16 && KS == 3) return launch_dgrad_s2<16, 32, 32, 3, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st);
-  if (CIN == 16 && KS == 1) return launch_dgrad_s2<16, 32, 32, 1, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st);
-  if (CIN == 32 && KS == 3) return launch_dgrad_s2<32, 64, 16, 3, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st);
-  if (CIN == 32 && KS == 1) return launch_dgrad_s2<32, 64, 16, 1, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st);
+  if (img) wt = image_of(w_img, COUT, KS * KS, CIN, 1);
+  if (CIN == 16 && KS == 3) return launch_dgrad_s2<16, 32, 32, 3, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st, img);
+  if (CIN == 16 && KS == 1) return launch_dgrad_s2<16, 32, 32, 1, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st, img);
+  if (CIN == 32 && KS == 3) return launch_dgrad_s2<32, 64, 16, 3, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st, img);
+  if (CIN == 32 && KS == 1) return launch_dgrad_s2<32, 64, 16, 1, 128>(dy, wt, dx, B, H_in, nlev, add, lazy, st, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+int alignq_conv_gen_nhwc_dgrad(const float* dy, const float* wt, float* dx, int B, int H_in, int W_in, int CIN, int COUT, int KS,
+                               int stride, int w_bit, const float* add, const float* bn_z, const float* bn_ab,
+                               const float* bn_save, const float* bn_ktot, const float* bn_dx_part, float* bn_dgamma,
+                               float* bn_dbeta, void* stream) {
+  return conv_gen_nhwc_dgrad(dy, wt, nullptr, dx, B, H_in, W_in, CIN, COUT, KS, stride, w_bit, add, bn_z, bn_ab, bn_save, bn_ktot,
+                             bn_dx_part, bn_dgamma, bn_dbeta, stream);
+}
+// the same reading the filter's data-gradient image (w_img as in alignq_conv_gen_nhwc_fwd_img)
+int alignq_conv_gen_nhwc_dgrad_img(const float* dy, const float* wt, const void* w_img, float* dx, int B, int H_in, int W_in,
+                                   int CIN, int COUT, int KS, int stride, int w_bit, const float* add, const float* bn_z,
+                                   const float* bn_ab, const float* bn_save, const float* bn_ktot, const float* bn_dx_part,
+                                   float* bn_dgamma, float* bn_dbeta, void* stream) {
+  if (!w_img) return ALIGNQ_EINVAL;
+  return conv_gen_nhwc_dgrad(dy, wt, w_img, dx, B, H_in, W_in, CIN, COUT, KS, stride, w_bit, add, bn_z, bn_ab, bn_save, bn_ktot,
+                             bn_dx_part, bn_dgamma, bn_dbeta, stream);
 }
 
 // Both convolutions of a transition block in one launch each way (shapes of alignq_conv_gen_nhwc_fwd; wt3 [COUT,3,3,CIN], wt1
 // [COUT,1,1,CIN], the same w_bit): y3 / y1 [B,H_in/2,W_in/2,COUT]; bn_part3 / bn_part1 as alignq_conv_gen_nhwc_fwd's for KS = 3 /
 // KS = 1.  Results are bit-identical to the two (forward) / four (backward) separate launches.
-int alignq_transition_nhwc_fwd(const float* x, const float* wt3, const float* wt1, float* y3, float* y1, int B, int H_in,
-                               int W_in, int CIN, int COUT, int w_bit, float* bn_part3, float* bn_part1, void* stream) {
-  if (!x || !wt3 || !wt1 || !y3 || !y1 || B < 1) return ALIGNQ_EINVAL;
+static int transition_nhwc_fwd(const float* x, const float* wt3, const float* wt1, const void* w_img3, const void* w_img1,
+                               float* y3, float* y1, int B, int H_in, int W_in, int CIN, int COUT, int w_bit, float* bn_part3,
+                               float* bn_part1, void* stream) {
+  if (!x || !wt3 || !wt1 || !y3 || !y1 || B < 1 || !w_img3 != !w_img1) return ALIGNQ_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(w_img3) | reinterpret_cast<uintptr_t>(w_img1)) & 15) return ALIGNQ_EUNSUPPORTED;
+  const bool img = w_img3 != nullptr;
   if (w_bit < 1 || w_bit > 8 || !alignq_conv_gen_bn_parts(B, H_in, W_in, CIN, COUT, 3, 2) ||
       !alignq_conv_gen_bn_parts(B, H_in, W_in, CIN, COUT, 1, 2))
     return ALIGNQ_EUNSUPPORTED;
@@ -1786,15 +1938,29 @@ int alignq_transition_nhwc_fwd(const float* x, const float* wt3, const float* wt
   hipStream_t st = (hipStream_t)stream;
   const float nlev = (float)((1 << w_bit) - 1);
   const int H = H_in / 2;
-  if (CIN == 16) return launch_transition_fwd<16, 32, 32, 64, 128>(x, wt3, wt1, y3, y1, B, H, nlev, bn_part3, bn_part1, st);
-  if (CIN == 32) return launch_transition_fwd<32, 64, 16, 32, 64>(x, wt3, wt1, y3, y1, B, H, nlev, bn_part3, bn_part1, st);
+  if (img) { wt3 = image_of(w_img3, COUT, 9, CIN, 0); wt1 = image_of(w_img1, COUT, 1, CIN, 0); }
+  if (CIN == 16) return launch_transition_fwd<16, 32, 32, 64, 128>(x, wt3, wt1, y3, y1, B, H, nlev, bn_part3, bn_part1, st, img);
+  if (CIN == 32) return launch_transition_fwd<32, 64, 16, 32, 64>(x, wt3, wt1, y3, y1, B, H, nlev, bn_part3, bn_part1, st, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+int alignq_transition_nhwc_fwd(const float* x, const float* wt3, const float* wt1, float* y3, float* y1, int B, int H_in,
+                               int W_in, int CIN, int COUT, int w_bit, float* bn_part3, float* bn_part1, void* stream) {
+  return transition_nhwc_fwd(x, wt3, wt1, nullptr, nullptr, y3, y1, B, H_in, W_in, CIN, COUT, w_bit, bn_part3, bn_part1, stream);
+}
+// the same with both roles reading their filter's forward image (w_img3 / w_img1: the image buffers for (COUT, 9, CIN) / (COUT, 1, CIN),
+// flip = 0)
+int alignq_transition_nhwc_fwd_img(const float* x, const float* wt3, const float* wt1, const void* w_img3, const void* w_img1,
+                                   float* y3, float* y1, int B, int H_in, int W_in, int CIN, int COUT, int w_bit,
+                                   float* bn_part3, float* bn_part1, void* stream) {
+  if (!w_img3 || !w_img1) return ALIGNQ_EINVAL;
+  return transition_nhwc_fwd(x, wt3, wt1, w_img3, w_img1, y3, y1, B, H_in, W_in, CIN, COUT, w_bit, bn_part3, bn_part1, stream);
 }
 
 // dx [B,H_in,W_in,CIN] = data gradient of BOTH convolutions (+ add), and the partial-sum slabs of both filter gradients
 // (ws3 / ws1 = alignq_conv_gen_wgrad_ws_bytes for KS = 3 / 1; *n_slabs3 / *n_slabs1 slabs are left for
 // alignq_conv3x3_wgrad_reduce_multi).  bn3_* / bn1_*: the lazy batch-norm form of dy3 / dy1 as in alignq_conv_gen_nhwc_dgrad.
-int alignq_transition_nhwc_bwd(const float* x, const float* dy3, const float* dy1, const float* wt3, const float* wt1,
+static int transition_nhwc_bwd(const float* x, const float* dy3, const float* dy1, const float* wt3, const float* wt1,
+                               const void* w_img3, const void* w_img1,
                                float* dx, void* ws3, void* ws1, int B, int H_in, int W_in, int CIN, int COUT, int w_bit,
                                int* n_slabs3, int* n_slabs1, const float* add,
                                const float* bn3_z, const float* bn3_ab, const float* bn3_save, const float* bn3_ktot,
@@ -1802,6 +1968,9 @@ int alignq_transition_nhwc_bwd(const float* x, const float* dy3, const float* dy
                                const float* bn1_z, const float* bn1_ab, const float* bn1_save, const float* bn1_ktot,
                                const float* bn1_dx_part, float* bn1_dgamma, float* bn1_dbeta, void* stream) {
   if (!x || !dy3 || !dy1 || !wt3 || !wt1 || !dx || !ws3 || !ws1 || !n_slabs3 || !n_slabs1 || B < 1) return ALIGNQ_EINVAL;
+  if (!w_img3 != !w_img1) return ALIGNQ_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(w_img3) | reinterpret_cast<uintptr_t>(w_img1)) & 15) return ALIGNQ_EUNSUPPORTED;
+  const bool img = w_img3 != nullptr;
   if (bn3_z && (!bn3_ab || !bn3_save || (!bn3_ktot && !bn3_dx_part))) return ALIGNQ_EINVAL;
   if (bn1_z && (!bn1_ab || !bn1_save || (!bn1_ktot && !bn1_dx_part))) return ALIGNQ_EINVAL;
   if (w_bit < 1 || w_bit > 8 || !alignq_conv_gen_bn_parts(B, H_in, W_in, CIN, COUT, 3, 2) ||
@@ -1818,13 +1987,38 @@ int alignq_transition_nhwc_bwd(const float* x, const float* dy3, const float* dy
   if (int rc = lazy_parts(lazy3, bn3_dx_part, bn3_dgamma, bn3_dbeta, B, COUT, HWo)) return rc;
   if (int rc = lazy_parts(lazy1, bn1_dx_part, bn1_dgamma, bn1_dbeta, B, COUT, HWo)) return rc;
   const int Ho = H_in / 2;
+  if (img) { wt3 = image_of(w_img3, COUT, 9, CIN, 1); wt1 = image_of(w_img1, COUT, 1, CIN, 1); }
   if (CIN == 16)
     return launch_transition_bwd<16, 32, 32, 64, 128, 256>(x, dy3, dy1, wt3, wt1, dx, (float*)ws3, (float*)ws1, B, Ho, nlev,
-                                                          n_slabs3, n_slabs1, add, lazy3, lazy1, st);
+                                                          n_slabs3, n_slabs1, add, lazy3, lazy1, st, img);
   if (CIN == 32)
     return launch_transition_bwd<32, 64, 16, 64, 64, 128>(x, dy3, dy1, wt3, wt1, dx, (float*)ws3, (float*)ws1, B, Ho, nlev,
-                                                         n_slabs3, n_slabs1, add, lazy3, lazy1, st);
+                                                         n_slabs3, n_slabs1, add, lazy3, lazy1, st, img);
   return ALIGNQ_EUNSUPPORTED;
+}
+int alignq_transition_nhwc_bwd(const float* x, const float* dy3, const float* dy1, const float* wt3, const float* wt1,
+                               float* dx, void* ws3, void* ws1, int B, int H_in, int W_in, int CIN, int COUT, int w_bit,
+                               int* n_slabs3, int* n_slabs1, const float* add,
+                               const float* bn3_z, const float* bn3_ab, const float* bn3_save, const float* bn3_ktot,
+                               const float* bn3_dx_part, float* bn3_dgamma, float* bn3_dbeta,
+                               const float* bn1_z, const float* bn1_ab, const float* bn1_save, const float* bn1_ktot,
+                               const float* bn1_dx_part, float* bn1_dgamma, float* bn1_dbeta, void* stream) {
+  return transition_nhwc_bwd(x, dy3, dy1, wt3, wt1, nullptr, nullptr, dx, ws3, ws1, B, H_in, W_in, CIN, COUT, w_bit, n_slabs3,
+                             n_slabs1, add, bn3_z, bn3_ab, bn3_save, bn3_ktot, bn3_dx_part, bn3_dgamma, bn3_dbeta, bn1_z, bn1_ab,
+                             bn1_save, bn1_ktot, bn1_dx_part, bn1_dgamma, bn1_dbeta, stream);
+}
+// the same with the data-gradient role reading both filters' data-gradient images (w_img3 / w_img1 as in alignq_transition_nhwc_fwd_img)
+int alignq_transition_nhwc_bwd_img(const float* x, const float* dy3, const float* dy1, const float* wt3, const float* wt1,
+                                   const void* w_img3, const void* w_img1, float* dx, void* ws3, void* ws1, int B, int H_in,
+                                   int W_in, int CIN, int COUT, int w_bit, int* n_slabs3, int* n_slabs1, const float* add,
+                                   const float* bn3_z, const float* bn3_ab, const float* bn3_save, const float* bn3_ktot,
+                                   const float* bn3_dx_part, float* bn3_dgamma, float* bn3_dbeta,
+                                   const float* bn1_z, const float* bn1_ab, const float* bn1_save, const float* bn1_ktot,
+                                   const float* bn1_dx_part, float* bn1_dgamma, float* bn1_dbeta, void* stream) {
+  if (!w_img3 || !w_img1) return ALIGNQ_EINVAL;
+  return transition_nhwc_bwd(x, dy3, dy1, wt3, wt1, w_img3, w_img1, dx, ws3, ws1, B, H_in, W_in, CIN, COUT, w_bit, n_slabs3,
+                             n_slabs1, add, bn3_z, bn3_ab, bn3_save, bn3_ktot, bn3_dx_part, bn3_dgamma, bn3_dbeta, bn1_z, bn1_ab,
+                             bn1_save, bn1_ktot, bn1_dx_part, bn1_dgamma, bn1_dbeta, stream);
 }
 
 // The stem convolution (3 -> 16 channels, 3x3, stride 1, padding 1, width 32): x [B,H,32,3], wt [16,3,3,3] (channels-last

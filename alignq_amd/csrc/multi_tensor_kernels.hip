@@ -41,6 +41,37 @@ struct WChunk {
   long n[kChunk];
 };
 
+// Pre-packed bf16 filter images for the convolutions of conv_kernels.hip ("Filter images"): the integer bins
+// b = (__bf16) rintf(W_q * (2^k - 1)) of a channels-last filter [CO][KK][CI], laid out so that a wave's A fragment of one k step
+// is one contiguous 1 KB (16 bytes per lane).  Two images back to back: F[CO/16][NSF][64][8] (forward: k = (tap, ci)) and
+// D[CI/16][NSD][64][8] (data gradient: k = (tap', co), tap' = KK - 1 - tap when `flip`).  Written by the launch that forms W_q,
+// from the register that is stored to q; the padding slots (k steps past the last tap) are written as +0 by the threads that
+// hold the last tap, so nothing depends on what the buffer held before.
+// 64 * (pointer + packed geometry word) = 768 B beside WChunk's 3072 B: the argument block stays inside 4 KB.
+struct WImgs {
+  unsigned short* img[kChunk];   // nullptr: this tensor has no images
+  unsigned geo[kChunk];          // CO | CI << 10 | KK << 20 | flip << 28
+};
+constexpr int kImgMaxC = 1023, kImgMaxKK = 255;
+
+__device__ __forceinline__ long img_slot(int row, int kk, int ns) {
+  return ((((long)(row >> 4) * ns + (kk >> 5)) * 64 + ((kk >> 3) & 3) * 16 + (row & 15)) << 3) + (kk & 7);
+}
+
+__device__ __forceinline__ void img_store(unsigned short* __restrict__ img, unsigned geo, long i, float qv, float nlev) {
+  const int CO = geo & 1023, CI = (geo >> 10) & 1023, KK = (geo >> 20) & 255;
+  const bool flip = (geo >> 28) & 1;
+  const int ci = (int)(i % CI), r = (int)(i / CI), t = r % KK, co = r / KK;
+  const unsigned short b = __builtin_bit_cast(unsigned short, (__bf16)rintf(qv * nlev));
+  const int nsf = (KK * CI + 31) >> 5, nsd = (KK * CO + 31) >> 5;
+  img[img_slot(co, t * CI + ci, nsf)] = b;
+  if (t == KK - 1 && ci < 32 * nsf - KK * CI) img[img_slot(co, KK * CI + ci, nsf)] = 0;
+  unsigned short* __restrict__ D = img + (long)(CO >> 4) * nsf * 512;
+  const int td = flip ? KK - 1 - t : t;
+  D[img_slot(ci, td * CO + co, nsd)] = b;
+  if (td == KK - 1 && co < 32 * nsd - KK * CO) D[img_slot(ci, KK * CO + co, nsd)] = 0;
+}
+
 __global__ __launch_bounds__(kThreads) void mt_weight_partial_kernel(WChunk c, double* __restrict__ ws, int t0) {
   __shared__ double sm[32];
   const int t = blockIdx.y;
@@ -68,9 +99,9 @@ __global__ __launch_bounds__(kThreads) void mt_weight_partial_kernel(WChunk c, d
   }
 }
 
-template <int FORMULA>
-__global__ __launch_bounds__(kThreads) void mt_weight_apply_kernel(WChunk c, const double* __restrict__ ws,
-                                                                   float* __restrict__ ms_out, int t0, int k) {
+template <int FORMULA, bool IMG>
+__device__ __forceinline__ void weight_apply_body(const WChunk& c, const double* __restrict__ ws, float* __restrict__ ms_out,
+                                                  int t0, int k, unsigned short* __restrict__ img, unsigned geo) {
   __shared__ double sm[32];
   __shared__ __attribute__((aligned(16))) float nerf_lds[ALIGNQ_NERF_LDS_FLOATS];
   nerf_tab_load(nerf_lds);                  // block_sum2d's barriers publish it
@@ -104,12 +135,24 @@ __global__ __launch_bounds__(kThreads) void mt_weight_apply_kernel(WChunk c, con
       const long i = MT_IDX(u);
       if (i < n) {
         float tt, b;
-        q[i] = weight_quant1<FORMULA>(v[u], wc, k, &tt, &b, tab);
+        const float qv = weight_quant1<FORMULA>(v[u], wc, k, &tt, &b, tab);
+        q[i] = qv;
         if (cdf) cdf[i] = tt;
         if (pdf) pdf[i] = weight_pdf2(v[u], wc);
+        if (IMG && img) img_store(img, geo, i, qv, (float)((1 << k) - 1));
       }
     }
   }
+}
+template <int FORMULA>
+__global__ __launch_bounds__(kThreads) void mt_weight_apply_kernel(WChunk c, const double* __restrict__ ws,
+                                                                   float* __restrict__ ms_out, int t0, int k) {
+  weight_apply_body<FORMULA, false>(c, ws, ms_out, t0, k, nullptr, 0u);
+}
+template <int FORMULA>
+__global__ __launch_bounds__(kThreads) void mt_weight_apply_img_kernel(WChunk c, WImgs im, const double* __restrict__ ws,
+                                                                       float* __restrict__ ms_out, int t0, int k) {
+  weight_apply_body<FORMULA, true>(c, ws, ms_out, t0, k, im.img[blockIdx.y], im.geo[blockIdx.y]);
 }
 
 // Statistics + quantisation in ONE launch for filters of at most kFusedMaxN elements (every CIFAR filter: 432 .. 36864; round 6: the
@@ -118,8 +161,9 @@ __global__ __launch_bounds__(kThreads) void mt_weight_apply_kernel(WChunk c, con
 // flight at once, the same order in every workgroup of the tensor, hence the same mean / std bits in all of them - instead of
 // meeting the other workgroups' partial sums in a second launch.  Needs n % 4 == 0 and 16-byte aligned filters (the launcher checks).
 constexpr int kFusedThreads = 1024, kFusedPerBlk = 2048, kFusedQuads = 9, kFusedMaxN = kFusedQuads * 4 * kFusedThreads;
-template <int FORMULA>
-__global__ __launch_bounds__(kFusedThreads) void mt_weight_fused_kernel(WChunk c, float* __restrict__ ms_out, int t0, int k) {
+template <int FORMULA, bool IMG>
+__device__ __forceinline__ void weight_fused_body(const WChunk& c, float* __restrict__ ms_out, int t0, int k,
+                                                  unsigned short* __restrict__ img, unsigned geo) {
   __shared__ double sm[32];
   __shared__ __attribute__((aligned(16))) float nerf_lds[ALIGNQ_NERF_LDS_FLOATS];
   const int t = blockIdx.y;
@@ -168,11 +212,23 @@ __global__ __launch_bounds__(kFusedThreads) void mt_weight_fused_kernel(WChunk c
     const long i = (long)blockIdx.x * kFusedPerBlk + threadIdx.x + u * kFusedThreads;
     if (i < n) {
       float tt, b;
-      q[i] = weight_quant1<FORMULA>(v[u], wc, k, &tt, &b, tab);
+      const float qv = weight_quant1<FORMULA>(v[u], wc, k, &tt, &b, tab);
+      q[i] = qv;
       if (cdf) cdf[i] = tt;
       if (pdf) pdf[i] = weight_pdf2(v[u], wc);
+      if (IMG && img) img_store(img, geo, i, qv, (float)((1 << k) - 1));
     }
   }
+}
+template <int FORMULA>
+__global__ __launch_bounds__(kFusedThreads) void mt_weight_fused_kernel(WChunk c, float* __restrict__ ms_out, int t0, int k) {
+  weight_fused_body<FORMULA, false>(c, ms_out, t0, k, nullptr, 0u);
+}
+// the same launch also writing the filter images (an instantiation of its own: the kernel above keeps its code)
+template <int FORMULA>
+__global__ __launch_bounds__(kFusedThreads) void mt_weight_fused_img_kernel(WChunk c, WImgs im, float* __restrict__ ms_out, int t0,
+                                                                            int k) {
+  weight_fused_body<FORMULA, true>(c, ms_out, t0, k, im.img[blockIdx.y], im.geo[blockIdx.y]);
 }
 
 __global__ __launch_bounds__(kThreads) void mt_weight_bwd_partial_kernel(WChunk c, const float* __restrict__ ms,
@@ -435,9 +491,16 @@ extern "C" {
 
 size_t alignq_weight_multi_ws_bytes(int T) { return (size_t)(T > 0 ? T : 1) * kMaxBlk * 2 * sizeof(double); }
 
-int alignq_weight_quant_fwd_multi(int T, const float* const* w, float* const* q, float* const* cdf_out,
+size_t alignq_filter_image_bytes(int CO, int KK, int CI) {
+  if (CO < 16 || CI < 16 || (CO & 15) || (CI & 15) || CO > kImgMaxC || CI > kImgMaxC || KK < 1 || KK > kImgMaxKK) return 0;
+  const size_t nsf = ((size_t)KK * CI + 31) / 32, nsd = ((size_t)KK * CO + 31) / 32;
+  return ((size_t)(CO / 16) * nsf + (size_t)(CI / 16) * nsd) * 512 * sizeof(unsigned short);
+}
+
+// shared by alignq_weight_quant_fwd_multi (img == nullptr: the kernels without images) and alignq_weight_quant_fwd_multi_img
+static int weight_quant_fwd_multi(int T, const float* const* w, float* const* q, float* const* cdf_out,
                                   float* const* pdf_out, const int64_t* n, float* ms, int k, int formula, void* ws,
-                                  void* stream) {
+                                  void* const* img, const int32_t* geom, void* stream) {
   if (T <= 0 || !w || !q || !n || !ms || !ws) return ALIGNQ_EINVAL;
   if (!((k >= 1 && k <= 16) || k == 32)) return ALIGNQ_EINVAL;
   if (formula != ALIGNQ_FORMULA_ADMM && formula != ALIGNQ_FORMULA_CDF) return ALIGNQ_EINVAL;
@@ -454,11 +517,30 @@ int alignq_weight_quant_fwd_multi(int T, const float* const* w, float* const* q,
       c.n[i] = (long)n[t0 + i];
       if (c.n[i] > max_n) max_n = c.n[i];
     }
+    WImgs im;
+    bool any_img = false;
+    for (int i = 0; i < cnt; i++) {
+      im.img[i] = nullptr; im.geo[i] = 0;
+      if (!img || !img[t0 + i]) continue;
+      if (!geom || k < 1 || k > 8) return ALIGNQ_EINVAL;       // the bins must be exact in bf16's 8 significant bits
+      const int32_t* g4 = geom + 4 * (size_t)(t0 + i);
+      const int CO = g4[0], KK = g4[1], CI = g4[2];
+      if (!alignq_filter_image_bytes(CO, KK, CI) || (long)CO * KK * CI != c.n[i]) return ALIGNQ_EINVAL;
+      if (reinterpret_cast<uintptr_t>(img[t0 + i]) & 15) return ALIGNQ_EUNSUPPORTED;
+      im.img[i] = (unsigned short*)img[t0 + i];
+      im.geo[i] = (unsigned)CO | (unsigned)CI << 10 | (unsigned)KK << 20 | (g4[3] ? 1u << 28 : 0u);
+      any_img = true;
+    }
     bool fused = max_n <= kFusedMaxN;
     for (int i = 0; i < cnt && fused; i++) fused = (c.n[i] & 3) == 0 && (reinterpret_cast<uintptr_t>(c.w[i]) & 15) == 0;
     if (fused) {            // small filters: statistics and quantisation in one launch (mt_weight_fused_kernel)
       dim3 fgrid((unsigned)((max_n + kFusedPerBlk - 1) / kFusedPerBlk), cnt);
-      if (formula == ALIGNQ_FORMULA_ADMM)
+      if (any_img) {
+        if (formula == ALIGNQ_FORMULA_ADMM)
+          hipLaunchKernelGGL((mt_weight_fused_img_kernel<0>), fgrid, kFusedThreads, 0, st, c, im, ms, t0, k);
+        else
+          hipLaunchKernelGGL((mt_weight_fused_img_kernel<1>), fgrid, kFusedThreads, 0, st, c, im, ms, t0, k);
+      } else if (formula == ALIGNQ_FORMULA_ADMM)
         hipLaunchKernelGGL((mt_weight_fused_kernel<0>), fgrid, kFusedThreads, 0, st, c, ms, t0, k);
       else
         hipLaunchKernelGGL((mt_weight_fused_kernel<1>), fgrid, kFusedThreads, 0, st, c, ms, t0, k);
@@ -468,13 +550,31 @@ int alignq_weight_quant_fwd_multi(int T, const float* const* w, float* const* q,
     dim3 grid(blocks_for(max_n), cnt);
     hipLaunchKernelGGL(mt_weight_partial_kernel, grid, kThreads, 0, st, c, (double*)ws, t0);
     LAUNCH_CHECK();
-    if (formula == ALIGNQ_FORMULA_ADMM)
+    if (any_img) {
+      if (formula == ALIGNQ_FORMULA_ADMM)
+        hipLaunchKernelGGL((mt_weight_apply_img_kernel<0>), grid, kThreads, 0, st, c, im, (const double*)ws, ms, t0, k);
+      else
+        hipLaunchKernelGGL((mt_weight_apply_img_kernel<1>), grid, kThreads, 0, st, c, im, (const double*)ws, ms, t0, k);
+    } else if (formula == ALIGNQ_FORMULA_ADMM)
       hipLaunchKernelGGL((mt_weight_apply_kernel<0>), grid, kThreads, 0, st, c, (const double*)ws, ms, t0, k);
     else
       hipLaunchKernelGGL((mt_weight_apply_kernel<1>), grid, kThreads, 0, st, c, (const double*)ws, ms, t0, k);
     LAUNCH_CHECK();
   }
   return 0;
+}
+
+int alignq_weight_quant_fwd_multi(int T, const float* const* w, float* const* q, float* const* cdf_out,
+                                  float* const* pdf_out, const int64_t* n, float* ms, int k, int formula, void* ws,
+                                  void* stream) {
+  return weight_quant_fwd_multi(T, w, q, cdf_out, pdf_out, n, ms, k, formula, ws, nullptr, nullptr, stream);
+}
+
+int alignq_weight_quant_fwd_multi_img(int T, const float* const* w, float* const* q, float* const* cdf_out,
+                                      float* const* pdf_out, const int64_t* n, float* ms, int k, int formula, void* ws,
+                                      void* const* img, const int32_t* geom, void* stream) {
+  if (!img || !geom) return ALIGNQ_EINVAL;
+  return weight_quant_fwd_multi(T, w, q, cdf_out, pdf_out, n, ms, k, formula, ws, img, geom, stream);
 }
 
 int alignq_weight_quant_bwd_multi(int T, const float* const* g, const float* const* w, const float* ms,

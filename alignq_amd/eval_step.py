@@ -35,13 +35,15 @@ class EvalStep(_CapturedStep):
     without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
     end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
 
-    def __init__(self, model, channels_last=True, qconv=True, pack_bins=True):
+    def __init__(self, model, channels_last=True, qconv=True, pack_bins=True, filter_images=True):
         if channels_last:
             model = model.to(memory_format=torch.channels_last)
         self.model = model
         self.channels_last = bool(channels_last)
         self.qconv = bool(qconv and channels_last and torch.cuda.is_available())
         self.pack_bins = bool(pack_bins and self.qconv)
+        # the quantiser's launch also writes the convolutions' bf16 filter images: once per evaluation, read by every batch
+        self.filter_images = bool(filter_images and self.qconv)
         self.all_convs = [m for m in model.modules() if hasattr(m, "quantize_fn")]
         self._office = hasattr(model, "feature") or hasattr(model, "feature_layers")
         self._acc = None             # include/alignq.h: {double sum ce, int64 top-1, int64 top-5, int64 rows}
@@ -83,7 +85,7 @@ class EvalStep(_CapturedStep):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
         evaluation refreshes the SAME tensors in place: a captured graph keeps reading them."""
         convs = [c for c in self.all_convs if getattr(c.quantize_fn, "w_bit", 32) != 32 and hasattr(c.quantize_fn, "_pre")]
-        fused.prequantize_weights(convs, pack=self.qconv and self._office)
+        fused.prequantize_weights(convs, pack=self.qconv and self._office, images=self.filter_images)
         fresh = {id(c): c.quantize_fn._pre for c in convs}
         if self._wq is not None and set(self._wq) == set(fresh):
             for key, old in self._wq.items():

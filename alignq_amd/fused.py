@@ -24,6 +24,11 @@ from . import _lib as L
 class WeightQuantAllFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, k, formula, *weights):
+        # a trailing non-tensor argument: per-weight filter-image buffers (uint8 tensors or None, see filter_image_geometry),
+        # written by the same launch (alignq_weight_quant_fwd_multi_img)
+        images = None
+        if weights and isinstance(weights[-1], (list, tuple)):
+            images, weights = weights[-1], weights[:-1]
         lib = L.load()
         ws_ = [L.dense_f32(w, "weight") for w in weights]
         T = len(ws_)
@@ -34,9 +39,18 @@ class WeightQuantAllFn(torch.autograd.Function):
         ms = torch.empty(T, 2, dtype=torch.float32, device=dev)
         scratch = torch.empty(lib.alignq_weight_multi_ws_bytes(T), dtype=torch.uint8, device=dev)
         n = L.i64_array([w.numel() for w in ws_])
-        L.check(lib.alignq_weight_quant_fwd_multi(T, L.ptr_array(ws_), L.ptr_array(qs), L.ptr_array(cs),
-                                                  L.ptr_array(ps), n, L.ptr(ms), int(k), int(formula), L.ptr(scratch),
-                                                  L.stream_ptr()), "alignq_weight_quant_fwd_multi")
+        if images is not None and any(im is not None for im in images):
+            geom = []
+            for w, im in zip(ws_, images):
+                geom += list(filter_image_geometry(w)) if im is not None else [0, 0, 0, 0]
+            L.check(lib.alignq_weight_quant_fwd_multi_img(T, L.ptr_array(ws_), L.ptr_array(qs), L.ptr_array(cs), L.ptr_array(ps), n,
+                                                          L.ptr(ms), int(k), int(formula), L.ptr(scratch), L.ptr_array(list(images)),
+                                                          (ctypes.c_int32 * len(geom))(*geom), L.stream_ptr()),
+                    "alignq_weight_quant_fwd_multi_img")
+        else:
+            L.check(lib.alignq_weight_quant_fwd_multi(T, L.ptr_array(ws_), L.ptr_array(qs), L.ptr_array(cs),
+                                                      L.ptr_array(ps), n, L.ptr(ms), int(k), int(formula), L.ptr(scratch),
+                                                      L.stream_ptr()), "alignq_weight_quant_fwd_multi")
         ctx.save_for_backward(ms, *ws_)
         ctx.set_materialize_grads(False)     # no zero tensors for the 2T non-differentiable cdf/pdf outputs
         ctx.mark_non_differentiable(*cs, *ps)
@@ -59,13 +73,32 @@ class WeightQuantAllFn(torch.autograd.Function):
         L.check(lib.alignq_weight_quant_bwd_multi(T, L.ptr_array(gs), L.ptr_array(list(ws_)), L.ptr(ms),
                                                   L.ptr_array(dws), L.i64_array([w.numel() for w in ws_]),
                                                   L.ptr(scratch), L.stream_ptr()), "alignq_weight_quant_bwd_multi")
-        return (None, None) + tuple(dws)
+        return (None, None) + tuple(dws) + ((None,) if len(ctx.needs_input_grad) > 2 + T else ())
 
 
-def prequantize_weights(convs, pack=False):
+def filter_image_geometry(w):
+    """(CO, KK, CI, flip) of a filter whose convolution reads pre-packed images (csrc/conv_kernels.hip: the ResNet body's 3x3
+    stride-1 filters, flip = 1, and the transition blocks' 3x3 / 1x1 filters, flip = 0), or None.  The storage must be
+    channels-last, [CO][KK][CI]."""
+    if w.dim() != 4 or not w.is_cuda or w.dtype != torch.float32:
+        return None
+    co, ci, kh, kw = w.shape
+    if not (w.is_contiguous(memory_format=torch.channels_last) or (kh == kw == 1 and w.is_contiguous())):
+        return None
+    if kh == kw == 3 and co == ci and co in (16, 32, 64):
+        return co, 9, ci, 1
+    if kh == kw and kh in (1, 3) and (ci, co) in ((16, 32), (32, 64)):
+        return co, kh * kw, ci, 0
+    return None
+
+
+def prequantize_weights(convs, pack=False, images=False):
     """convs: modules with `.weight` and `.quantize_fn` (Conv2d_Q).  All must share w_bit (< 32) and tree.
     pack: also leave every (<= 8-bit) filter's integer bins as bf16 / f16 bit patterns (ops.pack_filter_bins, one launch per 64
-    filters) for the GEMM convolutions of ops.QConvGemmFn."""
+    filters) for the GEMM convolutions of ops.QConvGemmFn.
+    images: the quantiser's own launch also writes the bf16 filter images of every `use_qconv` module whose geometry the
+    convolution kernels read images for (filter_image_geometry); parked as the sixth field of `_pre`, handed out by
+    weight_quantize_fn.take_image."""
     convs = [c for c in convs if c.quantize_fn.w_bit != 32]
     if not convs:
         return
@@ -73,7 +106,20 @@ def prequantize_weights(convs, pack=False):
     for c in convs:
         groups.setdefault((c.quantize_fn.w_bit, c.quantize_fn._formula), []).append(c)
     for (k, formula), cs in groups.items():
-        outs = WeightQuantAllFn.apply(k, formula, *[c.weight for c in cs])
+        imgs = None
+        if images and 1 <= k <= 8:
+            lib = L.load()
+            imgs = []
+            for c in cs:
+                geo = filter_image_geometry(c.weight) if getattr(c, "use_qconv", False) else None
+                imgs.append(None if geo is None else
+                            torch.empty(lib.alignq_filter_image_bytes(*geo[:3]), dtype=torch.uint8, device=c.weight.device))
+            if all(im is None for im in imgs):
+                imgs = None
+        if imgs is not None:
+            outs = WeightQuantAllFn.apply(k, formula, *[c.weight for c in cs], imgs)
+        else:
+            outs = WeightQuantAllFn.apply(k, formula, *[c.weight for c in cs])
         T = len(cs)
         bins = None
         if pack and 1 <= k <= 8:
@@ -83,7 +129,9 @@ def prequantize_weights(convs, pack=False):
             bins = dict(zip(sel, packed))
         for i, c in enumerate(cs):
             pre = (c.weight, outs[i], outs[T + i], outs[2 * T + i])
-            c.quantize_fn._pre = pre + ((bins[i],) if bins is not None and i in bins else ())
+            b = bins[i] if bins is not None and i in bins else None
+            im = imgs[i] if imgs is not None else None
+            c.quantize_fn._pre = pre + ((b, im) if im is not None else (b,) if b is not None else ())
 
 
 # ------------------------------------------------------------------------------------------------------------------

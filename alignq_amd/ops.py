@@ -586,8 +586,10 @@ class QConv3x3Fn(torch.autograd.Function):
     instead of by a separate accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, tap=False, bn_stats=False, xbins=None, a_bit=0):
-        """bn_stats=True: the kernel's epilogue also leaves per-workgroup per-channel {sum y, sum y^2}; they are attached to
+    def forward(ctx, x, w, w_bit, tap=False, bn_stats=False, xbins=None, a_bit=0, img=None):
+        """img: the filter's pre-packed bf16 images (weight_quantize_fn.take_image; a uint8 tensor written by the quantiser's launch
+        from this w): forward and data gradient read them in place of w (alignq_conv3x3_nhwc_img, bit-identical).
+        bn_stats=True: the kernel's epilogue also leaves per-workgroup per-channel {sum y, sum y^2}; they are attached to
         the output as `y._alignq_bn_part = (float tensor [C, parts, 2], parts)` for fused.bn_site, which then skips its own
         statistics pass over y.
         xbins (N2): x is only a HANDLE (fused.packed_handle: shape and autograd edge, no data); the activation is read from its
@@ -601,12 +603,18 @@ class QConv3x3Fn(torch.autograd.Function):
             n_parts = lib.alignq_conv3x3_bn_parts(B, H, W, C)
             part = torch.empty(C, n_parts, 2, dtype=torch.float32, device=dev) if n_parts > 0 else None
         xb = xbins.element_size() if xbins is not None else 0
-        L.check(lib.alignq_conv3x3_nhwc(None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, int(w_bit), 0,
-                                        None, L.ptr(part), L.ptr(xbins), xb, int(a_bit), L.stream_ptr()), "alignq_conv3x3_nhwc")
+        if img is not None:
+            L.check(lib.alignq_conv3x3_nhwc_img(None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(img), L.ptr(y), B, H, W, C,
+                                                int(w_bit), 0, None, L.ptr(part), L.ptr(xbins), xb, int(a_bit), L.stream_ptr()),
+                    "alignq_conv3x3_nhwc_img")
+        else:
+            L.check(lib.alignq_conv3x3_nhwc(None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, int(w_bit), 0,
+                                            None, L.ptr(part), L.ptr(xbins), xb, int(a_bit), L.stream_ptr()), "alignq_conv3x3_nhwc")
         if xbins is not None:
             ctx.save_for_backward(xbins, w)
         else:
             ctx.save_for_backward(x, w)
+        ctx.img = img
         ctx.packed = (xbins is not None, int(a_bit), (B, C, H, W))
         ctx.w_bit = int(w_bit)
         ctx.tap = bool(tap)
@@ -626,11 +634,11 @@ class QConv3x3Fn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def apply_with_stats(x, w, w_bit, tap=False, xbins=None, a_bit=0):
+    def apply_with_stats(x, w, w_bit, tap=False, xbins=None, a_bit=0, img=None):
         """apply(...) with bn_stats=True; attaches the partial statistics to the returned y (a plain python attribute)."""
         # the partials are created inside forward; fetch them through a one-slot mailbox (autograd hides ctx from callers)
         L.MB.conv3x3 = None
-        out = QConv3x3Fn.apply(x, w, w_bit, tap, True, xbins, a_bit)
+        out = QConv3x3Fn.apply(x, w, w_bit, tap, True, xbins, a_bit, img)
         y = out[0] if tap else out
         if L.MB.conv3x3 is not None:
             y._alignq_bn_part = L.MB.conv3x3
@@ -642,7 +650,8 @@ class QConv3x3Fn(torch.autograd.Function):
     def backward(ctx, gy, gtap=None):
         x, w = ctx.saved_tensors
         packed, a_bit, (B, C, H, W) = ctx.packed
-        none7 = (None,) * 5
+        none7 = (None,) * 6
+        img = ctx.img
         if gy is None:                     # only the shortcut alias was used downstream
             return (gtap, None) + none7
         lazy = fused.take_lazy_dz(ctx.link, gy)      # (g, z, ab, save, ktot): gy is the gradient w.r.t. the folded BN's OUTPUT
@@ -671,12 +680,17 @@ class QConv3x3Fn(torch.autograd.Function):
             # filler role: this launch also finishes slab reductions of convolutions whose backward already ran
             fill = pending.take(C)
             nf = len(fill)
-            L.check(lib.alignq_conv3x3_nhwc_bwd_fill(
-                xp, L.ptr(gy), L.ptr(w), L.ptr(dx), L.ptr(ws), B, H, W, C, ctx.w_bit, ctypes.byref(ns), L.ptr(add), L.ptr(bz),
-                L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart) if bk is None else None, L.ptr(bdg), L.ptr(bdb), xbp, xbb, a_bit,
-                nf, L.ptr_array([f[0] for f in fill]) if nf else None, L.ptr_array([f[1] for f in fill]) if nf else None,
-                (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
-                (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None, L.stream_ptr()), "alignq_conv3x3_nhwc_bwd_fill")
+            tail = (B, H, W, C, ctx.w_bit, ctypes.byref(ns), L.ptr(add), L.ptr(bz),
+                    L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart) if bk is None else None, L.ptr(bdg), L.ptr(bdb), xbp, xbb, a_bit,
+                    nf, L.ptr_array([f[0] for f in fill]) if nf else None, L.ptr_array([f[1] for f in fill]) if nf else None,
+                    (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
+                    (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None, L.stream_ptr())
+            if img is not None:
+                L.check(lib.alignq_conv3x3_nhwc_bwd_fill_img(xp, L.ptr(gy), L.ptr(w), L.ptr(img), L.ptr(dx), L.ptr(ws), *tail),
+                        "alignq_conv3x3_nhwc_bwd_fill_img")
+            else:
+                L.check(lib.alignq_conv3x3_nhwc_bwd_fill(xp, L.ptr(gy), L.ptr(w), L.ptr(dx), L.ptr(ws), *tail),
+                        "alignq_conv3x3_nhwc_bwd_fill")
             pending.add(ws, dw, ns.value, 9 * C * C)
             return (dx, dw) + none7
         if lazy is not None:               # not the fused path after all: finish the batch-norm input gradient here
@@ -686,8 +700,12 @@ class QConv3x3Fn(torch.autograd.Function):
             gy = gy.contiguous(memory_format=cl)
         if ctx.needs_input_grad[0]:
             dx = new_x()
-            L.check(lib.alignq_conv3x3_nhwc(L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add), None, None, 0, 0,
-                                            L.stream_ptr()), "alignq_conv3x3_nhwc")
+            if img is not None:
+                L.check(lib.alignq_conv3x3_nhwc_img(L.ptr(gy), L.ptr(w), L.ptr(img), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add),
+                                                    None, None, 0, 0, L.stream_ptr()), "alignq_conv3x3_nhwc_img")
+            else:
+                L.check(lib.alignq_conv3x3_nhwc(L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add), None, None, 0,
+                                                0, L.stream_ptr()), "alignq_conv3x3_nhwc")
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)          # channels-last [C,3,3,C] storage like w
             ws = _ws(lib.alignq_conv3x3_wgrad_ws_bytes(C), dev)
@@ -745,16 +763,22 @@ class QConvGenFn(torch.autograd.Function):
     is added in this data-gradient kernel's epilogue instead of by a separate accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, padding, tap=False):
+    def forward(ctx, x, w, w_bit, padding, tap=False, img=None):
+        """img: the filter's pre-packed bf16 images (as QConv3x3Fn's), read by the forward and the data gradient."""
         B, CIN, H, W = x.shape
         COUT, ks = w.shape[0], w.shape[2]
         lib = L.load()
         y = torch.empty((B, COUT, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         n_parts = lib.alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2)
         part = torch.empty(COUT, n_parts, 2, dtype=torch.float32, device=x.device)
-        L.check(lib.alignq_conv_gen_nhwc_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit), L.ptr(part),
-                                             L.stream_ptr()), "alignq_conv_gen_nhwc_fwd")
+        if img is not None:
+            L.check(lib.alignq_conv_gen_nhwc_fwd_img(L.ptr(x), L.ptr(w), L.ptr(img), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit),
+                                                     L.ptr(part), L.stream_ptr()), "alignq_conv_gen_nhwc_fwd_img")
+        else:
+            L.check(lib.alignq_conv_gen_nhwc_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit), L.ptr(part),
+                                                 L.stream_ptr()), "alignq_conv_gen_nhwc_fwd")
         ctx.save_for_backward(x, w)
+        ctx.img = img
         ctx.w_bit = int(w_bit)
         # 2: the data-gradient kernel reduces the site backward's per-tile sums and publishes the BN parameter gradients
         ctx.link = None
@@ -772,7 +796,7 @@ class QConvGenFn(torch.autograd.Function):
     def backward(ctx, gy, gtap=None):
         x, w = ctx.saved_tensors
         if gy is None:                     # only the alias was used downstream
-            return gtap, None, None, None, None
+            return gtap, None, None, None, None, None
         add = None if gtap is None else L.like_layout(gtap, x)
         lazy = fused.take_lazy_dz(ctx.link, gy)      # (g, z, ab, save, ktot): gy is the gradient w.r.t. the folded BN's OUTPUT
         gy = gy.contiguous(memory_format=torch.channels_last)
@@ -784,9 +808,13 @@ class QConvGenFn(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            L.check(lib.alignq_conv_gen_nhwc_dgrad(L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, CIN, COUT, ks, 2, ctx.w_bit,
-                                                   L.ptr(add), L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
-                                                   L.ptr(bdg), L.ptr(bdb), L.stream_ptr()), "alignq_conv_gen_nhwc_dgrad")
+            tail = (B, H, W, CIN, COUT, ks, 2, ctx.w_bit, L.ptr(add), L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
+                    L.ptr(bdg), L.ptr(bdb), L.stream_ptr())
+            if ctx.img is not None:
+                L.check(lib.alignq_conv_gen_nhwc_dgrad_img(L.ptr(gy), L.ptr(w), L.ptr(ctx.img), L.ptr(dx), *tail),
+                        "alignq_conv_gen_nhwc_dgrad_img")
+            else:
+                L.check(lib.alignq_conv_gen_nhwc_dgrad(L.ptr(gy), L.ptr(w), L.ptr(dx), *tail), "alignq_conv_gen_nhwc_dgrad")
         elif add is not None:
             dx = add
         if ctx.needs_input_grad[1]:        # split-bf16 MFMA, deterministic slabs
@@ -803,12 +831,12 @@ class QConvGenFn(torch.autograd.Function):
                 L.check(lib.alignq_conv_gen_nhwc_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, CIN, COUT, ks, 2,
                                                        None, L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
                                                        L.stream_ptr()), "alignq_conv_gen_nhwc_wgrad")
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
     @staticmethod
-    def apply_with_stats(x, w, w_bit, padding, tap=False):
+    def apply_with_stats(x, w, w_bit, padding, tap=False, img=None):
         L.MB.conv3x3 = None
-        out = QConvGenFn.apply(x, w, w_bit, padding, tap)
+        out = QConvGenFn.apply(x, w, w_bit, padding, tap, img)
         y = out[0] if tap else out
         if L.MB.conv3x3 is not None:
             y._alignq_bn_part = L.MB.conv3x3
@@ -824,7 +852,10 @@ class QTransitionFn(torch.autograd.Function):
 
 
     @staticmethod
-    def forward(ctx, x, w3, w1, w_bit):
+    def forward(ctx, x, w3, w1, w_bit, img3=None, img1=None):
+        """img3 / img1: both filters' pre-packed bf16 images (as QConv3x3Fn's; both or neither)."""
+        if img3 is None or img1 is None:
+            img3 = img1 = None
         B, CIN, H, W = x.shape
         COUT = w3.shape[0]
         lib = L.load()
@@ -835,10 +866,16 @@ class QTransitionFn(torch.autograd.Function):
         n1 = lib.alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, 1, 2)
         part3 = torch.empty(COUT, n3, 2, dtype=torch.float32, device=x.device)
         part1 = torch.empty(COUT, n1, 2, dtype=torch.float32, device=x.device)
-        L.check(lib.alignq_transition_nhwc_fwd(L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(y3), L.ptr(y1), B, H, W, CIN, COUT,
-                                               int(w_bit), L.ptr(part3), L.ptr(part1), L.stream_ptr()),
-                "alignq_transition_nhwc_fwd")
+        if img3 is not None:
+            L.check(lib.alignq_transition_nhwc_fwd_img(L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(img3), L.ptr(img1), L.ptr(y3), L.ptr(y1),
+                                                       B, H, W, CIN, COUT, int(w_bit), L.ptr(part3), L.ptr(part1), L.stream_ptr()),
+                    "alignq_transition_nhwc_fwd_img")
+        else:
+            L.check(lib.alignq_transition_nhwc_fwd(L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(y3), L.ptr(y1), B, H, W, CIN, COUT,
+                                                   int(w_bit), L.ptr(part3), L.ptr(part1), L.stream_ptr()),
+                    "alignq_transition_nhwc_fwd")
         ctx.save_for_backward(x, w3, w1)
+        ctx.imgs = (img3, img1)
         ctx.w_bit = int(w_bit)
         ctx.link3, ctx.link1 = fused.LazyLink(), fused.LazyLink()
         # mode 2: the data-gradient role reduces the site backward's per-tile sums and publishes the BN parameter gradients
@@ -863,10 +900,15 @@ class QTransitionFn(torch.autograd.Function):
         ws3 = _ws(lib.alignq_conv_gen_wgrad_ws_bytes(CIN, COUT, 3), x.device)
         ws1 = _ws(lib.alignq_conv_gen_wgrad_ws_bytes(CIN, COUT, 1), x.device)
         ns3, ns1 = ctypes.c_int(0), ctypes.c_int(0)
-        L.check(lib.alignq_transition_nhwc_bwd(
-            L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), L.ptr(dx), L.ptr(ws3), L.ptr(ws1), B, H, W, CIN, COUT,
-            ctx.w_bit, ctypes.byref(ns3), ctypes.byref(ns1), None, *[L.ptr(t) for t in f3], *[L.ptr(t) for t in f1],
-            L.stream_ptr()), "alignq_transition_nhwc_bwd")
+        tail = (L.ptr(dx), L.ptr(ws3), L.ptr(ws1), B, H, W, CIN, COUT, ctx.w_bit, ctypes.byref(ns3), ctypes.byref(ns1), None,
+                *[L.ptr(t) for t in f3], *[L.ptr(t) for t in f1], L.stream_ptr())
+        img3, img1 = ctx.imgs
+        if img3 is not None:
+            L.check(lib.alignq_transition_nhwc_bwd_img(L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), L.ptr(img3),
+                                                       L.ptr(img1), *tail), "alignq_transition_nhwc_bwd_img")
+        else:
+            L.check(lib.alignq_transition_nhwc_bwd(L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), *tail),
+                    "alignq_transition_nhwc_bwd")
         pending = fused.active_wgrads()
         if pending is not None:
             pending.add(ws3, dw3, ns3.value, 9 * CIN * COUT)
@@ -875,12 +917,12 @@ class QTransitionFn(torch.autograd.Function):
             L.check(lib.alignq_conv3x3_wgrad_reduce_multi(
                 2, L.ptr_array([ws3, ws1]), L.ptr_array([dw3, dw1]), (ctypes.c_int * 2)(ns3.value, ns1.value),
                 (ctypes.c_int * 2)(9 * CIN * COUT, CIN * COUT), L.stream_ptr()), "alignq_conv3x3_wgrad_reduce_multi")
-        return dx, dw3, dw1, None
+        return dx, dw3, dw1, None, None, None
 
     @staticmethod
-    def apply_with_stats(x, w3, w1, w_bit):
+    def apply_with_stats(x, w3, w1, w_bit, img3=None, img1=None):
         L.MB.transition = None
-        y3, y1 = QTransitionFn.apply(x, w3, w1, w_bit)
+        y3, y1 = QTransitionFn.apply(x, w3, w1, w_bit, img3, img1)
         if L.MB.transition is not None:
             y3._alignq_bn_part, y1._alignq_bn_part = L.MB.transition
             L.MB.transition = None

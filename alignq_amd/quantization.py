@@ -74,10 +74,13 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
             if not getattr(self, "_pre_keep", False):     # (EvalStep keeps the parked tensors for every batch of an evaluation: the filters do not change)
                 self._pre = None
             self._bins = None
+            self._image = None
             if pre is not None and pre[0] is x:
                 q, c, pdf = pre[1], pre[2], pre[3]
-                if len(pre) > 4:
+                if len(pre) > 4 and pre[4] is not None:
                     self._bins = (q.data_ptr(), pre[4])          # the filter's packed integer bins (fused.prequantize_weights(pack=True))
+                if len(pre) > 5 and pre[5] is not None:
+                    self._image = (q.data_ptr(), pre[5])         # its bf16 filter images (fused.prequantize_weights(images=True))
             else:
                 q, c, pdf = ops.WeightQuantFn.apply(x, self.w_bit, formula)
             if tree != "cdf":   # the CDF tree keeps these as locals (quantization.py:70-72)
@@ -92,6 +95,12 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
         def take_bins(self, weight_q):
             """(bf16, f16) bins of `weight_q` if the last forward left them (else None: the convolution packs them itself)."""
             held = getattr(self, "_bins", None)
+            return held[1] if held is not None and held[0] == weight_q.data_ptr() else None
+
+        def take_image(self, weight_q):
+            """The filter images the quantiser's launch wrote with `weight_q` (a uint8 tensor), else None: the convolution then
+            reads the fp32 filter."""
+            held = getattr(self, "_image", None)
             return held[1] if held is not None and held[0] == weight_q.data_ptr() else None
 
     def _plain_act(x, a_bit, stage):
@@ -266,7 +275,8 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                             and tuple(self.stride) == (1, 1) and tuple(self.padding) == (1, 1) and tuple(self.dilation) == (1, 1)
                             and tuple(weight_q.shape) == (C_, C_, 3, 3) and (C_, W_) in ((16, 32), (32, 16), (64, 8)) and H_ % 8 == 0
                             and 1 <= self.quantize_fn.w_bit <= 8 and weight_q.is_contiguous(memory_format=torch.channels_last)):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit)
+                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit,
+                                                               self.quantize_fn.take_image(weight_q))
                     if (getattr(self, "use_qconv", False) and bins.dtype == torch.int16 and ops.level_count(input)
                             and ops.qconv_gemm_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
                                                                self.groups, self.bias, self.quantize_fn.w_bit)):
@@ -286,9 +296,11 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit)
+                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit,
+                                                               img=self.quantize_fn.take_image(weight_q))
                     if ops.qconv_gen_supported(*args):
-                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0])
+                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0],
+                                                               img=self.quantize_fn.take_image(weight_q))
                     if ops.qconv_stem_supported(*args):
                         return ops.QConvStemFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit)
                     if ops.qconv_stem7_supported(*args):     # the Office stem (7x7, stride 2, 3 -> 64 channels)
@@ -317,9 +329,11 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, True)
+                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, True,
+                                                               img=self.quantize_fn.take_image(weight_q))
                     if ops.qconv_gen_supported(*args):      # transition block: the alias feeds the shortcut convolution
-                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0], True)
+                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0], True,
+                                                               img=self.quantize_fn.take_image(weight_q))
                 return self._conv(input, weight_q), input
 
         return Conv2d_Q

@@ -370,8 +370,11 @@ class _CapturedStep:
 
 class TrainStep(_CapturedStep):
     def __init__(self, model, lr=0.04, momentum=0.9, weight_decay=1e-4, grad_hook=None, defer_losses=True, fuse_bn=True,
-                 channels_last=False, qconv=True, pack_bins=True, device_hyper=False):
-        """device_hyper: the learning rate in device memory (alignq_amd.schedule): set_lr keeps a captured graph, and
+                 channels_last=False, qconv=True, pack_bins=True, device_hyper=False, filter_images=True):
+        """filter_images (with channels_last and qconv): the weight quantiser's launch also writes every body / transition filter's
+        integer bins as pre-packed bf16 images, which the convolution kernels read in place of the fp32 filter (bit-identical
+        results; csrc/conv_kernels.hip).
+        device_hyper: the learning rate in device memory (alignq_amd.schedule): set_lr keeps a captured graph, and
         set_schedule lets the graph walk a MultiStepLR table by itself.
         channels_last: keep activations and conv weights in torch.channels_last memory (values, parameter names and
         state_dict are unchanged).  MIOpen's NHWC convolution kernels need no layout transposes around the weight-gradient
@@ -391,6 +394,7 @@ class TrainStep(_CapturedStep):
                 if hasattr(m, "conv1") and hasattr(m, "act_q0") and hasattr(m, "bn0"):
                     m.pack_bins = True
         self.channels_last = channels_last
+        self.filter_images = bool(filter_images and channels_last and qconv and torch.cuda.is_available())
         self._wgrads = DeferredWgrads(fresh_grads=True) if (channels_last and qconv and torch.cuda.is_available()) else None
         self.model = model
         if fuse_bn:      # fold BN into the site kernels where shapes allow (training, 64 < batch <= 128); no-op otherwise
@@ -428,7 +432,7 @@ class TrainStep(_CapturedStep):
             self.optimizer_admm.zero_grad(set_to_none=set_to_none)
         if self.channels_last and x.dim() == 4:
             x = x.contiguous(memory_format=torch.channels_last)      # no-op for the captured static input
-        prequantize_weights(self.all_convs)     # all conv weights in two launches
+        prequantize_weights(self.all_convs, images=self.filter_images)     # all conv weights (and filter images) in one launch
         fused_head = self.channels_last and hasattr(model, "logit") and hasattr(model, "avgpool")
         model._features_only = fused_head
         ce = None

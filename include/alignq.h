@@ -221,6 +221,22 @@ int alignq_weight_quant_fwd_multi(int T, const float* const* w, float* const* q,
                                   void* ws, void* stream);
 int alignq_weight_quant_bwd_multi(int T, const float* const* g, const float* const* w, const float* ms,
                                   float* const* dw, const int64_t* n, void* ws, void* stream);
+/* alignq_weight_quant_fwd_multi that ALSO writes, in the same launch(es), the pre-packed bf16 filter images the convolution
+ * kernels read (alignq_conv3x3_nhwc_img, alignq_conv3x3_nhwc_bwd_fill_img).  img: HOST array of T device pointers, NULL for a
+ * tensor without images; geom: HOST int32[T][4] = {CO, KK, CI, flip} of the channels-last filter [CO][KK][CI] (read only where
+ * img[t] != NULL; CO, CI multiples of 16 and < 1024, KK < 256, CO*KK*CI == n[t]; 1 <= k <= 8).
+ * With b(co, t, ci) = (bf16) rintf(q[co][t][ci] * (2^k - 1)) the buffer img[t] (alignq_filter_image_bytes(CO, KK, CI) bytes, 16-byte
+ * aligned) receives two images of bf16 bit patterns back to back, each laid out so that lane (qq = lane >> 4, m = lane & 15) of a
+ * wave reads its A fragment of k step s as one 16-byte load and the wave reads one contiguous 1 KB:
+ *   F[CO/16][NSF][64][8], NSF = ceil(KK*CI/32):  F[g][s][16 qq + m][j] = b(16 g + m, t, c),    kk = 32 s + 8 qq + j, t = kk / CI, c = kk % CI
+ *   D[CI/16][NSD][64][8], NSD = ceil(KK*CO/32):  D[g][s][16 qq + m][j] = b(co, ts, 16 g + m),  kk = 32 s + 8 qq + j, t' = kk / CO,
+ *                                                co = kk % CO, ts = flip ? KK - 1 - t' : t'
+ * and +0 where t (t') >= KK.  Every slot, padding included, is written by the launch.  q, cdf, pdf and ms are written exactly as by
+ * alignq_weight_quant_fwd_multi, with the same number of launches.                                                             */
+size_t alignq_filter_image_bytes(int CO, int KK, int CI);      /* 0: geometry without images */
+int alignq_weight_quant_fwd_multi_img(int T, const float* const* w, float* const* q, float* const* cdf_out,
+                                      float* const* pdf_out, const int64_t* n, float* ms, int k, int formula, void* ws,
+                                      void* const* img, const int32_t* geom, void* stream);
 /* SGD over T parameters (utils/optimizer.py:212-255): w_cdf[t]/w_pdf[t] non-NULL marks tensor t as a member
  * of `idx` (its p.grad receives the sigmoid_d(transform(w_cdf))*w_pdf rewrite); first[t] != 0 marks a
  * momentum buffer created in this step.                                                               */
@@ -304,6 +320,12 @@ int alignq_site_reduce_loss_multi_head(int S, void* const* ws, float* const* D, 
 int alignq_conv3x3_bn_parts(int B, int H, int W, int C);   /* workgroups of the forward launch (0: unsupported shape) */
 int alignq_conv3x3_nhwc(const float* x, const float* wt, float* y, int B, int H, int W, int C, int w_bit, int dgrad,
                         const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit, void* stream);
+/* The same with the filter read from its images (w_img: the buffer alignq_weight_quant_fwd_multi_img wrote for geometry
+ * (C, 9, C, flip = 1) from this wt at this w_bit): one 16-byte load per k step and lane in place of the fp32 filter fetch and its
+ * rounding; dgrad = 0 reads F, dgrad = 1 reads D.  Bit-identical to alignq_conv3x3_nhwc.                                       */
+int alignq_conv3x3_nhwc_img(const float* x, const float* wt, const void* w_img, float* y, int B, int H, int W, int C, int w_bit,
+                            int dgrad, const float* add, float* bn_part, const void* x_bins, int x_bin_bytes, int a_bit,
+                            void* stream);
 /* x_bins (N2, forward only, may be NULL; x may then be NULL): the activation operand as the int8 / int16 (x_bin_bytes 1 / 2)
  * level indices of an a_bit-bit ADMM-formula activation quantiser (alignq_site_partials_bn bins_out: value = idx / (2^a_bit - 1),
  * idx already clamped by the fused ReLU): the index is exact in TWO bf16 terms (two instead of three MFMAs per k step, 1-2 B
@@ -448,6 +470,35 @@ int alignq_conv3x3_nhwc_bwd_fill(const float* x, const float* dy, const float* w
                             float* bn_dbeta, const void* x_bins, int x_bin_bytes, int a_bit, int n_fill,
                                  const void* const* fill_ws, float* const* fill_dw, const int* fill_n_slabs,
                                  const int* fill_n_elem, void* stream);
+/* alignq_conv3x3_nhwc_bwd_fill whose data-gradient role reads the filter's D image (w_img as in alignq_conv3x3_nhwc_img).
+ * Bit-identical.                                                                                                              */
+int alignq_conv3x3_nhwc_bwd_fill_img(const float* x, const float* dy, const float* wt, const void* w_img, float* dx, void* ws,
+                                     int B, int H, int W, int C, int w_bit, int* n_slabs_out, const float* add,
+                                     const float* bn_z, const float* bn_ab, const float* bn_save, const float* bn_ktot,
+                                     const float* bn_dx_part, float* bn_dgamma, float* bn_dbeta, const void* x_bins,
+                                     int x_bin_bytes, int a_bit, int n_fill, const void* const* fill_ws, float* const* fill_dw,
+                                     const int* fill_n_slabs, const int* fill_n_elem, void* stream);
+/* The transition convolutions (alignq_conv_gen_nhwc_fwd / _dgrad, alignq_transition_nhwc_fwd / _bwd, declared below) reading
+ * their filters from images: w_img (w_img3 / w_img1) is the buffer alignq_weight_quant_fwd_multi_img wrote for geometry
+ * (COUT, KS*KS, CIN, flip = 0) from the same wt at the same w_bit.  The forward roles read F; the data-gradient roles read D, the 1x1
+ * shortcut's D image supplying the k steps behind the 3x3's in the one-launch backward.  Bit-identical to the entry points without
+ * an image; the filter-gradient roles do not read the filter.                                                                 */
+int alignq_conv_gen_nhwc_fwd_img(const float* x, const float* wt, const void* w_img, float* y, int B, int H_in, int W_in, int CIN,
+                                 int COUT, int KS, int stride, int w_bit, float* bn_part, void* stream);
+int alignq_conv_gen_nhwc_dgrad_img(const float* dy, const float* wt, const void* w_img, float* dx, int B, int H_in, int W_in,
+                                   int CIN, int COUT, int KS, int stride, int w_bit, const float* add, const float* bn_z,
+                                   const float* bn_ab, const float* bn_save, const float* bn_ktot, const float* bn_dx_part,
+                                   float* bn_dgamma, float* bn_dbeta, void* stream);
+int alignq_transition_nhwc_fwd_img(const float* x, const float* wt3, const float* wt1, const void* w_img3, const void* w_img1,
+                                   float* y3, float* y1, int B, int H_in, int W_in, int CIN, int COUT, int w_bit,
+                                   float* bn_part3, float* bn_part1, void* stream);
+int alignq_transition_nhwc_bwd_img(const float* x, const float* dy3, const float* dy1, const float* wt3, const float* wt1,
+                                   const void* w_img3, const void* w_img1, float* dx, void* ws3, void* ws1, int B, int H_in,
+                                   int W_in, int CIN, int COUT, int w_bit, int* n_slabs3, int* n_slabs1, const float* add,
+                                   const float* bn3_z, const float* bn3_ab, const float* bn3_save, const float* bn3_ktot,
+                                   const float* bn3_dx_part, float* bn3_dgamma, float* bn3_dbeta,
+                                   const float* bn1_z, const float* bn1_ab, const float* bn1_save, const float* bn1_ktot,
+                                   const float* bn1_dx_part, float* bn1_dgamma, float* bn1_dbeta, void* stream);
 /* bn_z != NULL: `dy` is not the convolution output's gradient but g, the gradient w.r.t. the OUTPUT of the training-mode
  * batch-norm that follows the convolution (what alignq_site_bwd_apply_bn writes); both roles form
  * dy = a[c] * (g - k0[c] - (z - mean[c]) * invstd[c] * k1[c]) on load from bn_z (the convolution's forward output), bn_ab,
