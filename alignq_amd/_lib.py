@@ -191,6 +191,10 @@ SIGNATURES = {
     "alignq_weight_quant_fwd_multi_img": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "alignq_filter_image_bytes": (_sz, [_i, _i, _i]),
     "alignq_weight_quant_bwd_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alignq_packed_bytes": (_sz, [_i64, _i]),
+    "alignq_weight_code_bits": (_i, [_i, _i]),
+    "alignq_weight_pack_multi": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "alignq_weight_unpack_multi": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alignq_sgd_step_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _f, _f, _vp]),
     "alignq_sgd_admm_step_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _f, _f,
                                         _i, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),

@@ -12,6 +12,7 @@
 #include "../../include/alignq.h"
 #include "admm_body.h"
 #include "alignq_math.h"
+#include "filter_image.h"
 
 using namespace alignq;
 
@@ -41,36 +42,12 @@ struct WChunk {
   long n[kChunk];
 };
 
-// Pre-packed bf16 filter images for the convolutions of conv_kernels.hip ("Filter images"): the integer bins
-// b = (__bf16) rintf(W_q * (2^k - 1)) of a channels-last filter [CO][KK][CI], laid out so that a wave's A fragment of one k step
-// is one contiguous 1 KB (16 bytes per lane).  Two images back to back: F[CO/16][NSF][64][8] (forward: k = (tap, ci)) and
-// D[CI/16][NSD][64][8] (data gradient: k = (tap', co), tap' = KK - 1 - tap when `flip`).  Written by the launch that forms W_q,
-// from the register that is stored to q; the padding slots (k steps past the last tap) are written as +0 by the threads that
-// hold the last tap, so nothing depends on what the buffer held before.
+// The filter images of filter_image.h (img_store) ride along with the launch that forms W_q.
 // 64 * (pointer + packed geometry word) = 768 B beside WChunk's 3072 B: the argument block stays inside 4 KB.
 struct WImgs {
   unsigned short* img[kChunk];   // nullptr: this tensor has no images
   unsigned geo[kChunk];          // CO | CI << 10 | KK << 20 | flip << 28
 };
-constexpr int kImgMaxC = 1023, kImgMaxKK = 255;
-
-__device__ __forceinline__ long img_slot(int row, int kk, int ns) {
-  return ((((long)(row >> 4) * ns + (kk >> 5)) * 64 + ((kk >> 3) & 3) * 16 + (row & 15)) << 3) + (kk & 7);
-}
-
-__device__ __forceinline__ void img_store(unsigned short* __restrict__ img, unsigned geo, long i, float qv, float nlev) {
-  const int CO = geo & 1023, CI = (geo >> 10) & 1023, KK = (geo >> 20) & 255;
-  const bool flip = (geo >> 28) & 1;
-  const int ci = (int)(i % CI), r = (int)(i / CI), t = r % KK, co = r / KK;
-  const unsigned short b = __builtin_bit_cast(unsigned short, (__bf16)rintf(qv * nlev));
-  const int nsf = (KK * CI + 31) >> 5, nsd = (KK * CO + 31) >> 5;
-  img[img_slot(co, t * CI + ci, nsf)] = b;
-  if (t == KK - 1 && ci < 32 * nsf - KK * CI) img[img_slot(co, KK * CI + ci, nsf)] = 0;
-  unsigned short* __restrict__ D = img + (long)(CO >> 4) * nsf * 512;
-  const int td = flip ? KK - 1 - t : t;
-  D[img_slot(ci, td * CO + co, nsd)] = b;
-  if (td == KK - 1 && co < 32 * nsd - KK * CO) D[img_slot(ci, KK * CO + co, nsd)] = 0;
-}
 
 __global__ __launch_bounds__(kThreads) void mt_weight_partial_kernel(WChunk c, double* __restrict__ ws, int t0) {
   __shared__ double sm[32];
@@ -523,12 +500,11 @@ static int weight_quant_fwd_multi(int T, const float* const* w, float* const* q,
       im.img[i] = nullptr; im.geo[i] = 0;
       if (!img || !img[t0 + i]) continue;
       if (!geom || k < 1 || k > 8) return ALIGNQ_EINVAL;       // the bins must be exact in bf16's 8 significant bits
-      const int32_t* g4 = geom + 4 * (size_t)(t0 + i);
-      const int CO = g4[0], KK = g4[1], CI = g4[2];
-      if (!alignq_filter_image_bytes(CO, KK, CI) || (long)CO * KK * CI != c.n[i]) return ALIGNQ_EINVAL;
+      const unsigned geo = img_geo_word(geom + 4 * (size_t)(t0 + i), c.n[i]);
+      if (!geo) return ALIGNQ_EINVAL;
       if (reinterpret_cast<uintptr_t>(img[t0 + i]) & 15) return ALIGNQ_EUNSUPPORTED;
       im.img[i] = (unsigned short*)img[t0 + i];
-      im.geo[i] = (unsigned)CO | (unsigned)CI << 10 | (unsigned)KK << 20 | (g4[3] ? 1u << 28 : 0u);
+      im.geo[i] = geo;
       any_img = true;
     }
     bool fused = max_n <= kFusedMaxN;

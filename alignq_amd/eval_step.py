@@ -15,7 +15,10 @@ Differences from the reference's test(): an ADMM site comp
 leaves ADMM.D alone (test() discards the loss, and the D it stores is overwritten by the next training forward before anything
 reads it); ties are ranked as include/alignq.h states for alignq_eval_metrics.  This holds where alignq_bnq_eval_fwd applies
 (channels-last fp32, C a power of two in [4, 2048], a quantiser of 1..16 bits or none): any other site runs today's `model.eval()`
-composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D."""
+composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D.
+
+    ev = EvalStep(skeleton, weights=export.PackedModel.load(path))     # evaluate from packed k-bit codes (export.py): begin()
+                                                                       # unpacks them; the model's fp32 filters are never read"""
 from __future__ import annotations
 
 import numpy as np
@@ -35,7 +38,9 @@ class EvalStep(_CapturedStep):
     without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
     end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
 
-    def __init__(self, model, channels_last=True, qconv=True, pack_bins=True, filter_images=True):
+    def __init__(self, model, channels_last=True, qconv=True, pack_bins=True, filter_images=True, weights=None):
+        if weights is not None and not channels_last:
+            raise ValueError("EvalStep(weights=): packed filters are channels-last; channels_last=True is required")
         if channels_last:
             model = model.to(memory_format=torch.channels_last)
         self.model = model
@@ -50,6 +55,12 @@ class EvalStep(_CapturedStep):
         self._saved = None           # module flags and training modes to restore
         self._wq = None              # the parked quantised filters (persistent: a captured graph reads them)
         self._scope = None
+        # weights: an export.PackedModel - begin() forms W_q, bins and images from its codes instead of quantising model's fp32
+        # filters, whose values are then never read (every quantised Conv2d_Q must match an entry: ValueError here, before any launch)
+        self._packed = None
+        if weights is not None:
+            from .export import PackedFilters
+            self._packed = PackedFilters(weights, model)
         self._init_capture(None)
 
     # ------------------------------------------------------------------------------------------- lifecycle
@@ -85,6 +96,16 @@ class EvalStep(_CapturedStep):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
         evaluation refreshes the SAME tensors in place: a captured graph keeps reading them."""
         convs = [c for c in self.all_convs if getattr(c.quantize_fn, "w_bit", 32) != 32 and hasattr(c.quantize_fn, "_pre")]
+        if self._packed is not None:
+            # from the packed codes (alignq_weight_unpack_multi) into tensors that persist: (weight, q, no cdf, no pdf, bins, image)
+            outs = self._packed.refresh(pack=self.qconv and self._office, images=self.filter_images)
+            if self._wq is None or any(self._wq.get(id(c), (None, None))[1] is not outs[id(c)][0] for c in convs):
+                self._graph = None
+            self._wq = {id(c): (c.weight, outs[id(c)][0], None, None, outs[id(c)][1], outs[id(c)][2]) for c in convs}
+            for c in convs:
+                c.quantize_fn._pre = self._wq[id(c)]
+                c.quantize_fn._pre_keep = True
+            return
         fused.prequantize_weights(convs, pack=self.qconv and self._office, images=self.filter_images)
         fresh = {id(c): c.quantize_fn._pre for c in convs}
         if self._wq is not None and set(self._wq) == set(fresh):

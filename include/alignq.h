@@ -237,6 +237,35 @@ size_t alignq_filter_image_bytes(int CO, int KK, int CI);      /* 0: geometry wi
 int alignq_weight_quant_fwd_multi_img(int T, const float* const* w, float* const* q, float* const* cdf_out,
                                       float* const* pdf_out, const int64_t* n, float* ms, int k, int formula, void* ws,
                                       void* const* img, const int32_t* geom, void* stream);
+/* ---- packed k-bit weights: W_q as bit-packed level codes, and back (DESIGN.md "Packed weights") ----------------------------------
+ * What is packed is weight_quantize_fn.forward's weight_q (cdf_alignment_admm/<model>/model/quantization.py:71-85, cdf_alignment/<model>/
+ * model/quantization.py:62-78).  With k = w_bit in 1..16, n = 2^k - 1 and b = rintf(W_q * n) (the integer level of uniform_quantize,
+ * quantization.py:23-31; sign() for k == 1 as in the kernels):
+ *   ALIGNQ_FORMULA_ADMM (levels -n..n):  code = b + n           bits = k + 1
+ *   ALIGNQ_FORMULA_CDF  (W_q = 2 i/n - 1):          code = i = (b + n)/2   bits = k
+ * Dequantisation is the quantiser's last step, one IEEE fp32 division: (code - n)/n, or (code/n)*2 - 1.  A code has no sign of zero:
+ * the ADMM tree's W_q = -0 comes back as +0, so dequantised values are bit-equal to W_q + 0.0f (== W_q); the CDF tree has no -0.
+ * Stream of a tensor of n elements in storage order (4-D filters: channels-last, [CO][KH][KW][CI]): groups of 32 elements; group g is
+ * the 32*bits-bit little-endian integer in the uint32 words [g*bits, g*bits + bits), element e of the group its bits
+ * [e*bits, (e+1)*bits); the last group is zero-padded; alignq_packed_bytes(n, bits) = ceil(n/32)*bits*4 bytes (0: n < 0 or bits
+ * outside 1..17).  alignq_weight_code_bits: `bits` above (0: k outside 1..16 or an unknown formula).
+ * Both launchers follow the multi-tensor forms above: HOST tables of T entries passed by value in chunks of 64 (one launch per chunk),
+ * hipGraph-capturable, NULL / size errors answered with ALIGNQ_EINVAL before anything is launched.
+ * alignq_weight_pack_multi: codes[t] (alignq_packed_bytes(n[t], bits) bytes, 4-byte aligned) from q[t]; every word is written,
+ *   padding included.  An element is BAD when no code dequantises to it (dequant(code) != q: NaN, infinities, values off the grid or
+ *   out of range): its code is 0 and *bad, a DEVICE int32 the caller has zeroed, is incremented (atomic add).
+ * alignq_weight_unpack_multi: per tensor, from codes[t]: fp32 W_q into q[t] (16-byte aligned); the bf16 / f16 bins exactly as
+ *   alignq_qconv_pack_weights writes them from that W_q (8-byte aligned; any n); the two filter images exactly as
+ *   alignq_weight_quant_fwd_multi_img defines them (geom rows {CO, KK, CI, flip}, alignq_filter_image_bytes, 16-byte aligned, every slot
+ *   written).  Any output table may be NULL and any entry may be NULL: nothing is written for it (all four tables NULL:
+ *   ALIGNQ_EINVAL).  A bins or img entry with k > 8, or an img entry whose geom row alignq_weight_quant_fwd_multi_img refuses:
+ *   ALIGNQ_EINVAL; a misaligned buffer: ALIGNQ_EUNSUPPORTED.                                                                     */
+size_t alignq_packed_bytes(int64_t n, int bits);
+int alignq_weight_code_bits(int k, int formula);
+int alignq_weight_pack_multi(int T, const float* const* q, const int64_t* n, int k, int formula, void* const* codes, int32_t* bad,
+                             void* stream);
+int alignq_weight_unpack_multi(int T, const void* const* codes, const int64_t* n, int k, int formula, float* const* q,
+                               void* const* bins_bf16, void* const* bins_f16, void* const* img, const int32_t* geom, void* stream);
 /* SGD over T parameters (utils/optimizer.py:212-255): w_cdf[t]/w_pdf[t] non-NULL marks tensor t as a member
  * of `idx` (its p.grad receives the sigmoid_d(transform(w_cdf))*w_pdf rewrite); first[t] != 0 marks a
  * momentum buffer created in this step.                                                               */
