@@ -209,6 +209,11 @@ SIGNATURES = {
     "alignq_eval_metrics": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "alignq_data_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _c.c_uint64, _i, _i, _vp, _i, _vp, _vp]),
     "alignq_data_crop_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _c.c_uint64, _i, _vp, _i, _vp, _vp]),
+    "alignq_dwconv3x3_supported": (_i, [_i] * 5),
+    "alignq_dwconv3x3_nhwc_fwd": (_i, [_vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "alignq_dwconv3x3_nhwc_dgrad": (_i, [_vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "alignq_dwconv3x3_wgrad_ws_bytes": (_i64, [_i] * 5),
+    "alignq_dwconv3x3_nhwc_wgrad": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
 }
 
 _lib = None

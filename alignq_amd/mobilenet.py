@@ -1,0 +1,101 @@
+"""MobileNet-V2 for SVHN, wired like the reference's cdf_alignment/mobilenet-v2-svhn/model/mobilenetV2.py (:25-135) on the CDF-only
+namespace (alignq_amd.cdf_alignment), with the SAME attribute names (`conv1`, `bn1`, `act_q1`, `layers[i].{act_q1,act_q2,act_q3,
+act_skip,conv1,bn1,conv2,bn2,conv3,bn3,shortcut.{0,1}}`, `conv2`, `bn2`, `act_q2`, `linear`), so that state_dict() keys and shapes
+equal the reference's and its checkpoints load by name.
+
+What the reference does and this file keeps: `cfg` is a class attribute; EVERY stride-1 block has the shortcut convolution +
+batch-norm + `act_skip` + ReLU, also where in_planes == out_planes; ReLU6 follows act_q1 / act_q2 of a block and nothing follows
+act_q3; the shortcut is added in place; the head is AvgPool2d(4) (a 4x4 map for 32x32 inputs), kept as `self.out`, and
+Linear(1280, num_classes).
+
+Every weight and activation quantiser runs on this repository's kernels.  With use_hip_convs(model) and channels-last inputs the
+depthwise 3x3 convolutions (`layers[i].conv2`) run on csrc/dwconv_kernels.hip and the pointwise ones whose channel counts are
+multiples of 64 on the exact-product GEMMs; the other convolutions, batch-norm and the linear layer go to MIOpen / rocBLAS through
+PyTorch-ROCm.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import cdf_alignment as _cdf
+
+
+class Block(nn.Module):
+    """Inverted residual: 1x1 expansion, depthwise 3x3 (stride), 1x1 projection; a convolutional shortcut at stride 1."""
+
+    def __init__(self, stage, wbit, abit, in_planes, out_planes, expansion, stride):
+        super().__init__()
+        self.stride = stride
+        planes = expansion * in_planes
+        Conv2d = _cdf.conv2d_Q_fn(w_bit=wbit, stage=stage)
+        for name in ("act_q1", "act_q2", "act_q3", "act_skip"):
+            setattr(self, name, _cdf.activation_quantize_fn(a_bit=abit, stage=stage))
+        self.conv1 = Conv2d(in_planes, planes, kernel_size=1, stride=1, padding=0, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, groups=planes, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = Conv2d(planes, out_planes, kernel_size=1, stride=1, padding=0, bias=False)
+        self.bn3 = nn.BatchNorm2d(out_planes)
+        self.relu = nn.ReLU6()
+        self.shortcut = None
+        if stride == 1:
+            self.shortcut = nn.Sequential(Conv2d(in_planes, out_planes, kernel_size=1, stride=1, padding=0, bias=False),
+                                          nn.BatchNorm2d(out_planes), self.act_skip, nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        out = self.relu(self.act_q1(self.bn1(self.conv1(x))))
+        out = self.relu(self.act_q2(self.bn2(self.conv2(out))))
+        out = self.act_q3(self.bn3(self.conv3(out)))
+        if self.stride == 1:
+            out += self.shortcut(x)
+        return out
+
+
+class MobileNetV2(nn.Module):
+    # (expansion, out_planes, num_blocks, stride)
+    cfg = [(1, 16, 1, 1), (6, 24, 2, 1), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
+
+    def __init__(self, block, wbit, abit, stage, num_classes=10):
+        super().__init__()
+        Conv2d = _cdf.conv2d_Q_fn(w_bit=wbit, stage=stage)
+        self.act_q1 = _cdf.activation_quantize_fn(a_bit=abit, stage=stage)
+        self.act_q2 = _cdf.activation_quantize_fn(a_bit=abit, stage=stage)
+        self.conv1 = Conv2d(3, 32, kernel_size=3, stride=1, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(32)
+        self.layers = self._make_layers(block, wbit, abit, stage, in_planes=32)
+        self.conv2 = Conv2d(320, 1280, kernel_size=1, stride=1, padding=0, bias=False)
+        self.bn2 = nn.BatchNorm2d(1280)
+        self.linear = nn.Linear(1280, num_classes)
+        self.relu = nn.ReLU(inplace=True)
+        self.avg_pool2d = nn.AvgPool2d(4)
+
+    def _make_layers(self, block, wbit, abit, stage, in_planes):
+        layers = []
+        for expansion, out_planes, num_blocks, stride in self.cfg:
+            for s in [stride] + [1] * (num_blocks - 1):
+                layers.append(block(stage, wbit, abit, in_planes, out_planes, expansion, s))
+                in_planes = out_planes
+        return nn.Sequential(*layers)
+
+    def forward(self, x):
+        out = self.relu(self.act_q1(self.bn1(self.conv1(x))))
+        out = self.layers(out)
+        out = self.relu(self.act_q2(self.bn2(self.conv2(out))))
+        self.out = self.avg_pool2d(out)
+        return self.linear(self.out.view(self.out.size(0), -1))
+
+
+def mobile_v2(wbit, abit, stage, num_classes=10):
+    return MobileNetV2(Block, wbit, abit, stage, num_classes=num_classes)
+
+
+def use_hip_convs(model):
+    """Channels-last parameters plus `use_qconv` on every Conv2d_Q (what TrainStep(channels_last=True, qconv=True) does for its
+    models): with channels-last inputs the convolutions this repository has kernels for then run on them.  Values, parameter
+    names and state_dict are unchanged."""
+    model = model.to(memory_format=torch.channels_last)
+    for m in model.modules():
+        if hasattr(m, "quantize_fn"):
+            m.use_qconv = True
+    return model

@@ -1217,3 +1217,56 @@ class QConvStemFn(torch.autograd.Function):
             y._alignq_bn_part = L.MB.conv3x3
             L.MB.conv3x3 = None
         return y
+
+
+def qconv_dw_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The depthwise convolutions alignq_dwconv3x3_nhwc_fwd implements (MobileNet-V2's `conv2`): groups == C_in == C_out, filter
+    (C, 1, 3, 3), padding 1, dilation 1, stride 1 or 2, no bias, channels-last fp32 input, C % 4 == 0.  Any w_bit: the kernels read
+    the fp32 W_q, whatever produced it (also the w_bit == 32 pass-through)."""
+    if bias is not None or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1) or tuple(stride) not in ((1, 1), (2, 2)):
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32):
+        return False
+    B, C, H, W = x.shape
+    if groups != C or tuple(w.shape) != (C, 1, 3, 3) or not w.is_contiguous():
+        return False
+    if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
+        return False
+    return L.load().alignq_dwconv3x3_supported(B, H, W, C, stride[0]) == 1
+
+
+class QConvDwFn(torch.autograd.Function):
+    """Conv2d_Q's depthwise 3x3 convolution (mobilenetV2.py:40) on alignq_dwconv3x3_nhwc_fwd; data gradient
+    (alignq_dwconv3x3_nhwc_dgrad) and filter gradient (alignq_dwconv3x3_nhwc_wgrad) each run only where a gradient is asked for.
+    x channels-last [B, C, H, W], w = W_q (C, 1, 3, 3); y channels-last.  No batch-norm by-product, no filter image."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride=1):
+        B, C, H, W = x.shape
+        s = int(stride)
+        y = torch.empty((B, C, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device,
+                        memory_format=torch.channels_last)
+        L.check(L.load().alignq_dwconv3x3_nhwc_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, s, L.stream_ptr()),
+                "alignq_dwconv3x3_nhwc_fwd")
+        ctx.save_for_backward(x, w)
+        ctx.stride = s
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        B, C, H, W = x.shape
+        s = ctx.stride
+        lib = L.load()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            L.check(lib.alignq_dwconv3x3_nhwc_dgrad(L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, C, s, L.stream_ptr()),
+                    "alignq_dwconv3x3_nhwc_dgrad")
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(w)
+            ws = _ws(lib.alignq_dwconv3x3_wgrad_ws_bytes(B, H, W, C, s), x.device)
+            L.check(lib.alignq_dwconv3x3_nhwc_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, C, s, L.stream_ptr()),
+                    "alignq_dwconv3x3_nhwc_wgrad")
+        return dx, dw, None

@@ -317,6 +317,8 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                                                                     ops.level_count(input), fused.conv_groups(), bins)
                         return ops.QConvGemmFn.apply(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
                                                      ops.level_count(input), 1, False, bins)
+                    if ops.qconv_dw_supported(*args):        # MobileNet-V2's depthwise 3x3 (csrc/dwconv_kernels.hip)
+                        return ops.QConvDwFn.apply(input, weight_q, self.stride[0])
                 return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
             def forward_with_shortcut(self, input):

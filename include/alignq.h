@@ -903,6 +903,32 @@ int alignq_data_crop_batch(const uint8_t* images, const int64_t* labels, const i
                            const float* lut, int64_t N, int side, int crop, int span, int off0, int B, int rank, int world,
                            uint64_t seed, int flip, float* x_out, int nhwc, int64_t* y_out, void* stream);
 
+/* ---- depthwise 3x3 convolution (csrc/dwconv_kernels.hip) ----
+ * The depthwise convolution of MobileNet-V2's blocks (cdf_alignment/mobilenet-v2-svhn/model/mobilenetV2.py:40: Conv2d_Q(planes, planes,
+ * kernel_size=3, stride=stride, padding=1, groups=planes, bias=False), whose F.conv2d call is model/quantization.py's Conv2d_Q.forward)
+ * and its two gradients, which the reference leaves to autograd.
+ *   Supported: fp32; activations channels-last [B][H][W][C]; filter wq [C][1][3][3] (element c * 9 + ky * 3 + kx: its contiguous and its
+ *   channels-last layout are the same memory); padding 1, dilation 1, no bias, stride 1 or 2; C % 4 == 0, C >= 4; any B, H_in, W_in >= 1
+ *   with B * H_in * W_in * C <= 2^31 - 1 (element offsets are int32); every pointer 16-byte aligned.  Anything else: ALIGNQ_EUNSUPPORTED;
+ *   a null pointer: ALIGNQ_EINVAL; both before anything touches a device.  alignq_dwconv3x3_supported answers the shape part: 1 / 0.
+ *   H_out = (H_in - 1) / stride + 1, W_out likewise (PyTorch's size for padding 1).  x, dx: [B][H_in][W_in][C]; y, dy: [B][H_out][W_out][C].
+ *   Arithmetic, every product and every sum one IEEE-754 fp32 operation (fl), taps (ky, kx) in row-major order:
+ *     forward        acc = +0;  acc = fl(acc + fl(x[b, ho * s + ky - 1, wo * s + kx - 1, c] * wq[c, ky, kx])) for every tap that lies
+ *                    inside the input (a tap in the padding is skipped);  y[b, ho, wo, c] = acc.
+ *     data gradient  acc = +0;  with hh = h + 1 - ky, ww = w + 1 - kx: where s divides hh and ww and (hh / s, ww / s) lies inside the
+ *                    output, acc = fl(acc + fl(dy[b, hh / s, ww / s, c] * wq[c, ky, kx]));  dx[b, h, w, c] = acc (+0 where no output
+ *                    reads the input position, as at stride 2).
+ *     filter gradient  dw[c, ky, kx] = sum over (b, ho, wo) of x[b, ho * s + ky - 1, wo * s + kx - 1, c] * dy[b, ho, wo, c], taps in the
+ *                    padding skipped; fp32 products and sums in an order that is a function of the shape alone (partial sums per slab of
+ *                    output pixels in ws, then one fixed-order pass; no atomics): two launches on the same inputs give the same bits.
+ *   ws: alignq_dwconv3x3_wgrad_ws_bytes(...) bytes (a multiple of 256; 0 for an unsupported shape), no initialisation needed.          */
+int alignq_dwconv3x3_supported(int B, int H_in, int W_in, int C, int stride);
+int alignq_dwconv3x3_nhwc_fwd(const float* x, const float* wq, float* y, int B, int H_in, int W_in, int C, int stride, void* stream);
+int alignq_dwconv3x3_nhwc_dgrad(const float* dy, const float* wq, float* dx, int B, int H_in, int W_in, int C, int stride, void* stream);
+int64_t alignq_dwconv3x3_wgrad_ws_bytes(int B, int H_in, int W_in, int C, int stride);
+int alignq_dwconv3x3_nhwc_wgrad(const float* x, const float* dy, float* dw, void* ws, int B, int H_in, int W_in, int C, int stride,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
