@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import typing
 
 import torch
 
@@ -404,22 +405,65 @@ class LazyLink:
 _posted_links = []
 
 
+class ConvStats(typing.NamedTuple):
+    """What a float-family convolution of ops leaves on its output as `y._alignq_bn_part` (its apply_with_stats): the epilogue's
+    per-workgroup {sum y, sum y^2}, fp32 [C, n_parts, 2].  lazy: 0 - the producer's backward never runs (the BN site finishes its
+    own input gradient); 1 - it accepts a lazy batch-norm gradient; 2 - it also reduces the site backward's per-tile sums itself and
+    writes the batch-norm parameter gradients.  link: through it the BN site's backward hands the record to that node (lazy > 0)."""
+    part: torch.Tensor
+    n_parts: int
+    lazy: int = 0
+    link: typing.Optional[LazyLink] = None
+
+
+class ConvStatsQ(typing.NamedTuple):
+    """The GEMM family's partials on `y._alignq_bnq_part`: fp64 [groups, n_parts, C_out, 2] for `groups` batch slices (conv_partials)"""
+    part: torch.Tensor
+    n_parts: int
+    groups: int
+
+
+class LazyBN(typing.NamedTuple):
+    """A lazy batch-norm gradient: g is the gradient w.r.t. the folded batch-norm's OUTPUT; the consuming convolution kernels form
+    dz = a*(g - k0 - zhat*k1) on load from z, ab, save and the totals ktot - or, ktot None, reduce the site backward's per-tile sums
+    `part` themselves and fill the parameter gradients dgamma / dbeta, which autograd already holds."""
+    g: typing.Any = None
+    z: typing.Any = None
+    ab: typing.Any = None
+    save: typing.Any = None
+    ktot: typing.Any = None
+    part: typing.Any = None
+    dgamma: typing.Any = None
+    dbeta: typing.Any = None
+
+    def operands(self, need_totals_now=False, B=0, C=0, HW=0):
+        """The seven tensors in the order include/alignq.h declares them: bn_z, bn_ab, bn_save, bn_ktot, bn_dx_part, bn_dgamma,
+        bn_dbeta (bn_dx_part only where there are no totals).  need_totals_now: the caller's kernels cannot publish the parameter
+        gradients, so a record without totals gets them here (alignq_bn_bwd_totals)."""
+        ktot = self.ktot
+        if ktot is None and need_totals_now and self.part is not None:
+            ktot = torch.empty(2, C, dtype=torch.float32, device=self.part.device)
+            L.check(L.load().alignq_bn_bwd_totals(L.ptr(self.part), B, C, HW, L.ptr(ktot), L.ptr(self.dgamma), L.ptr(self.dbeta),
+                                                  L.stream_ptr()), "alignq_bn_bwd_totals")
+        return self.z, self.ab, self.save, ktot, (self.part if ktot is None else None), self.dgamma, self.dbeta
+
+
+NO_LAZY_BN = LazyBN()          # nothing was posted: seven NULL operands, the incoming gradient is dz itself
+
+
 def post_lazy_dz(link, g, z, ab, save, ktot, part=None, dgamma=None, dbeta=None):
-    """ktot None: the consumer reduces the site backward's per-tile sums `part` itself (alignq_conv3x3_nhwc_bwd) and fills the
-    batch-norm parameter gradients dgamma / dbeta, which autograd already holds."""
-    link.record = (g, z, ab, save, ktot, part, dgamma, dbeta)
+    link.record = LazyBN(g, z, ab, save, ktot, part, dgamma, dbeta)
     _posted_links.append(link)
 
 
 def take_lazy_dz(link, g):
-    """The record posted for this convolution's output gradient, or None.  Raises if a record exists but the incoming
+    """The record posted for this convolution's output gradient, or NO_LAZY_BN.  Raises if a record exists but the incoming
     gradient is not the posted tensor (it was altered or summed with another gradient on the way)."""
     flush_bwd_twins()            # (a parked site backward writes what the record below points at)
     if link is None or link.record is None:
-        return None
+        return NO_LAZY_BN
     rec, link.record = link.record, None
-    posted = rec[0]
-    if g is None or g.data_ptr() != posted.data_ptr() or g.shape != posted.shape or g.stride() != posted.stride():
+    if g is None or g.data_ptr() != rec.g.data_ptr() or g.shape != rec.g.shape or g.stride() != rec.g.stride():
         raise RuntimeError(
             "alignq_amd: the gradient reaching the convolution is not the lazy batch-norm gradient its BN site posted "
             "(a tensor hook / retain_grad on the convolution output, or a second consumer of it, stands in between). "
@@ -553,11 +597,13 @@ class BNSiteFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bn_weight, bn_bias, running_mean, running_var, nbt, momentum, bn_eps, alterD, gamma, k, act_range,
-                eps, mu, rho, relu, rec=None, res=None, conv_part=None, pack=False):
-        """pack (N2; only with relu and without a residual): the output is NOT written as fp32; the kernel stores
-        the int8 / int16 level index of relu(x_q) instead (1-2 B per element) and the first return value is a data-less HANDLE
-        (`packed_handle`) carrying it as `._alignq_bins = (bins, k)` for a consumer that reads indices (ops.QConv3x3Fn:
-        forward and filter gradient); this node's own backward takes the ReLU mask from the index as well."""
+                eps, mu, rho, relu, rec=None, res=None, conv_part=None, pack=False, bins=None):
+        """conv_part: the ConvStats the convolution that produced z left on it.
+        pack (N2; only with relu and without a residual): the output is NOT written as fp32; the kernel stores
+        the int8 / int16 level index of relu(x_q) into the caller's `bins` (z's shape and strides, 1-2 B per element) and the first
+        return value is a data-less HANDLE (`packed_handle`) on which the caller hangs `._alignq_bins = (bins, k)` for a consumer
+        that reads indices (ops.QConv3x3Fn: forward and filter gradient); this node's own backward takes the ReLU mask from the
+        index as well."""
         z = L.dense_f32(z, "conv output")
         ctx.twin_bwd = None
         nhwc = not z.is_contiguous()             # dense_f32 only lets contiguous or channels-last 4-D tensors through
@@ -578,23 +624,16 @@ class BNSiteFn(torch.autograd.Function):
         conv_parts = 0
         if nhwc and conv_part is not None:
             # the convolution that produced z left per-workgroup partial statistics: no pass over z here
-            ws_bn, conv_parts = conv_part[0], conv_part[1]
+            ws_bn, conv_parts = conv_part.part, conv_part.n_parts
         elif nhwc:
             ws_bn = torch.empty(lib.alignq_bn_nhwc_ws_bytes(C), dtype=torch.uint8, device=dev)
             L.check(lib.alignq_bn_partial_stats_nhwc(L.ptr(z), B, C, HW, L.ptr(ws_bn), st), "alignq_bn_partial_stats_nhwc")
         else:
             ws_bn = torch.empty(lib.alignq_bn_ws_bytes(C), dtype=torch.uint8, device=dev)
             L.check(lib.alignq_bn_partial_stats(L.ptr(z), B, C, HW, L.ptr(ws_bn), st), "alignq_bn_partial_stats")
-        bins = None
-        if pack:
-            from . import ops
-            bdt = ops.bin_dtype(k, act_range, L.FORMULA_ADMM)
-            if not relu or res is not None or bdt is None or F % 4:
-                raise RuntimeError("BNSiteFn(pack=True) needs relu, no residual, k <= 16 and F % 4 == 0")
-            bins = torch.empty_strided(z.shape, z.stride(), dtype=bdt, device=dev)
-            y = None
-        else:
-            y = torch.empty_like(z)
+        if pack and (not relu or res is not None or bins is None or F % 4):
+            raise RuntimeError("BNSiteFn(pack=True) needs relu, no residual, F % 4 == 0 and the int8 / int16 `bins` to fill")
+        y = None if pack else torch.empty_like(z)
         D = torch.empty(B, B, dtype=torch.float32, device=dev)
         stats = torch.empty(4, F, dtype=torch.float32, device=dev)
         scal = rec.scal if rec is not None else torch.empty(4, dtype=torch.float32, device=dev)
@@ -623,18 +662,15 @@ class BNSiteFn(torch.autograd.Function):
             L.check(lib.alignq_site_reduce_loss(L.ptr(ws), B, F, L.ptr(D), L.ptr(A), L.ptr(Gm), dim, float(mu),
                                                 float(rho), L.ptr(scal), st), "alignq_site_reduce_loss")
         ctx.rec = rec
-        ctx.from_qconv = int(conv_part[2]) if (nhwc and conv_part is not None and len(conv_part) > 3) else 0
-        ctx.link = conv_part[3] if ctx.from_qconv else None
+        ctx.from_qconv = conv_part.lazy if (nhwc and conv_part is not None) else 0
+        ctx.link = conv_part.link if ctx.from_qconv else None
         ctx.bn_params = (bn_weight, bn_bias)
         ctx.save_for_backward(z, ab, save, stats, D, A, Gm, scal, y if (relu and not pack) else None, bins)
         ctx.set_materialize_grads(False)
         ctx.cfg = (float(act_range), float(eps), float(mu), bn_weight is not None, bn_bias is not None, res is not None,
                    int(nhwc))
         ctx.mark_non_differentiable(D)
-        if pack:
-            y = packed_handle(z.shape, dev)
-            L.MB.site_bins = (bins, int(k))
-        return y, scal[0], D
+        return (packed_handle(z.shape, dev) if pack else y), scal[0], D
 
 
     @staticmethod
@@ -690,7 +726,7 @@ class BNSiteFn(torch.autograd.Function):
             # copy the still unwritten buffer otherwise); the buffers themselves travel with the lazy record.
             post_lazy_dz(ctx.link, dx, z, ab, save, None, part, dgam, dbet)
             return (dx, None if dgam is None else dgam.view_as(dgam), None if dbet is None else dbet.view_as(dbet), None, None,
-                    None, None, None, dA, dG, None, None, None, None, None, None, None, dres, None, None)
+                    None, None, None, dA, dG, None, None, None, None, None, None, None, dres, None, None, None)
         if ctx.from_qconv and active_wgrads() is not None:
             # z is the output of one of ops' convolutions and a whole-model backward is running: only the per-channel totals
             # are computed here; the convolution's backward forms dz = a*(g - k0 - zhat*k1) on load (no elementwise pass)
@@ -699,11 +735,11 @@ class BNSiteFn(torch.autograd.Function):
                     "alignq_bn_bwd_totals")
             post_lazy_dz(ctx.link, dx, z, ab, save, ktot)
             return (dx, dgam, dbet, None, None, None, None, None, dA, dG, None, None, None, None, None, None, None, dres, None,
-                    None)
+                    None, None)
         dz = torch.empty_like(z)
         L.check(lib.alignq_bn_bwd_apply(L.ptr(dx), L.ptr(z), L.ptr(ab), L.ptr(save), L.ptr(part), B, C, HW, nhwc, L.ptr(dz),
                                         L.ptr(dgam), L.ptr(dbet), st), "alignq_bn_bwd_apply")
-        return (dz, dgam, dbet, None, None, None, None, None, dA, dG, None, None, None, None, None, None, None, dres, None, None)
+        return (dz, dgam, dbet, None, None, None, None, None, dA, dG, None, None, None, None, None, None, None, dres, None, None, None)
 
 
 def packed_handle(shape, device):
@@ -786,16 +822,17 @@ def bn_site(bn, act, z, eps=0.0, relu=False, residual=None, pack=False):
     admm = act.opt
     deferred = active_deferred()
     rec = deferred.new_record(z.shape[0], z.device) if deferred is not None else None
-    pack = bool(pack and relu and residual is None and _is_nhwc(z) and act.a_bit <= 8 and (z.shape[1] * z.shape[2] * z.shape[3]) % 4 == 0
-                and ops.bin_dtype(act.a_bit, config.args.act_range, L.FORMULA_ADMM) is not None)   # a large act_range has no narrow form
-    L.MB.site_bins = None
+    bdt = None
+    if pack and relu and residual is None and _is_nhwc(z) and act.a_bit <= 8 and (z.shape[1] * z.shape[2] * z.shape[3]) % 4 == 0:
+        bdt = ops.bin_dtype(act.a_bit, config.args.act_range, L.FORMULA_ADMM)      # (None: a large act_range has no narrow form)
+    pack = bdt is not None
+    bins = torch.empty_strided(z.shape, z.stride(), dtype=bdt, device=z.device) if pack else None
     y, loss, D = BNSiteFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn.momentum, bn.eps, admm.alterD, admm.gamma, act.a_bit, config.args.act_range, eps,
                                 admm.mu, admm.rho, relu, rec, residual,
-                                getattr(z, "_alignq_bn_part", None) if _is_nhwc(z) else None, pack)
+                                getattr(z, "_alignq_bn_part", None) if _is_nhwc(z) else None, pack, bins)
     if pack:
-        y._alignq_bins = L.MB.site_bins
-        L.MB.site_bins = None
+        y._alignq_bins = (bins, int(act.a_bit))
     admm.D = D
     if deferred is not None:
         if rec is not None:
@@ -819,7 +856,7 @@ class BNQuantReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, weight, bias, running_mean, running_var, nbt, momentum, bn_eps, k, act_range, formula, relu, groups=1,
-                residual=None, conv_part=None, pack=False):
+                residual=None, conv_part=None, pack=False, bins=None):
         """residual: added to the quantised value before the ReLU in the same pass (the CDF-only block's `out += shortcut;
         relu`); its gradient - the masked upstream gradient - is a second output of the backward's apply pass."""
         z = L.dense_f32(z, "conv output")
@@ -833,9 +870,10 @@ class BNQuantReluFn(torch.autograd.Function):
         ab = torch.empty(groups, 2, C, dtype=torch.float32, device=dev)
         save = torch.empty(groups, 2, C, dtype=torch.float32, device=dev)
         # pack (N2 on the Office path; the caller checked: ADMM formula, no residual, int16 index, f16-exact range): the output is NOT
-        # written as fp32; the kernel stores the ReLU-clamped level index as int16 and the function returns a data-less handle
-        # (packed_handle) that carries it as `._alignq_bins` for consumers that read indices (ops.QConvGemmFn)
-        bins = torch.empty(z.shape, dtype=torch.int16, device=dev, memory_format=torch.channels_last) if pack else None
+        # written as fp32; the kernel stores the ReLU-clamped level index into the caller's channels-last int16 `bins` and the function
+        # returns a data-less handle (packed_handle) on which the caller hangs `._alignq_bins` for consumers that read indices
+        if pack and bins is None:
+            raise RuntimeError("BNQuantReluFn(pack=True) needs the int16 `bins` to fill")
         y = None if pack else torch.empty_like(z)
         ws = torch.empty(lib.alignq_bnq_ws_bytes(C, groups), dtype=torch.uint8, device=dev)
         # the ReLU mask the backward needs, one bit per element (round 4): the node keeps 1/32 of a tensor instead of reading the
@@ -851,7 +889,6 @@ class BNQuantReluFn(torch.autograd.Function):
                 "alignq_bnq_fwd_parts")
         if pack:
             y = packed_handle(z.shape, dev)
-            L.MB.bnq_bins = (bins, int(k))
         ctx.save_for_backward(z, (mask if mask is not None else y) if relu else None, ab, save)
         ctx.bitmask = mask is not None
         ctx.has_res = residual is not None
@@ -879,7 +916,7 @@ class BNQuantReluFn(torch.autograd.Function):
                 "alignq_bnq_bwd")
         if ctx.has_res and not relu and ctx.needs_input_grad[13]:
             dres = g
-        return dz, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, dres, None, None
+        return dz, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, dres, None, None, None
 
 
 
@@ -978,9 +1015,9 @@ def conv_groups():
 def conv_partials(z, groups):
     """(partials, parts) a GEMM convolution left on its output for `groups` batch slices (ops.QConvGemmFn.apply_with_stats), or None"""
     rec = getattr(z, "_alignq_bnq_part", None)
-    if rec is None or rec[2] != int(groups):
+    if rec is None or rec.groups != int(groups):
         return None
-    return rec[0], rec[1]
+    return rec.part, rec.n_parts
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1469,12 +1506,11 @@ def bn_act_relu(bn, act, z, formula, relu=True, groups=1, residual=None, pack=Fa
                 and L.load().alignq_bin_bytes(int(act.a_bit), float(config.args.act_range), int(formula)) == 2
                 and float(config.args.act_range) * (2 ** int(act.a_bit) - 1) <= 2048.0
                 and float(config.args.act_range) == int(config.args.act_range))
-    L.MB.bnq_bins = None
-    y = BNQuantReluFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum,
-                            bn.eps, act.a_bit, config.args.act_range, formula, relu, groups, residual, conv_partials(z, groups), pack)
+    bins = torch.empty(z.shape, dtype=torch.int16, device=z.device, memory_format=torch.channels_last) if pack else None
+    y = BNQuantReluFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                            act.a_bit, config.args.act_range, formula, relu, groups, residual, conv_partials(z, groups), pack, bins)
     if pack:
-        y._alignq_bins = L.MB.bnq_bins
-        L.MB.bnq_bins = None
+        y._alignq_bins = (bins, int(act.a_bit))
     if residual is None:
         tag_levels(y, act.a_bit, config.args.act_range, formula)
     return y

@@ -557,22 +557,55 @@ def site_res_supported(x, residual) -> bool:
 
 
 # ------------------------------------------------------------------------------------------------ R9 (Conv2d_Q's conv)
-def qconv3x3_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
-    """Shapes alignq_conv3x3_nhwc implements: channels-last fp32, 3x3 / stride 1 / padding 1, C_in == C_out in {16,32,64}
-    at width 32 / 16 / 8 (the ResNet-20/56 body), a <= 8-bit quantised filter.  Everything else stays on MIOpen."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8):
+def qconv3x3_shape_supported(shape, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """Shapes alignq_conv3x3_nhwc implements, for an input given by its SHAPE only (a packed handle, fused.packed_handle): 3x3 /
+    stride 1 / padding 1, C_in == C_out in {16,32,64} at width 32 / 16 / 8 (the ResNet-20/56 body), a <= 8-bit quantised filter."""
+    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or len(shape) != 4:
         return False
     if tuple(stride) != (1, 1) or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32):
+    B, C, H, W = shape
+    if w.dtype != torch.float32 or tuple(w.shape) != (C, C, 3, 3) or (C, W) not in ((16, 32), (32, 16), (64, 8)):
         return False
-    B, C, H, W = x.shape
-    if tuple(w.shape) != (C, C, 3, 3) or (C, W) not in ((16, 32), (32, 16), (64, 8)):
+    # tiles are 8 / 8 / 4-8 whole image rows
+    return H % 8 == 0 and w.is_contiguous(memory_format=torch.channels_last)
+
+
+def qconv3x3_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """qconv3x3_shape_supported for a channels-last fp32 tensor.  Everything else stays on MIOpen."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return False
-    if H % 8:            # tiles are 8 / 8 / 4-8 whole image rows
+    if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
         return False
-    cl = torch.channels_last
-    return (x.is_contiguous(memory_format=cl) and not x.is_contiguous()) and w.is_contiguous(memory_format=cl)
+    return qconv3x3_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
+
+
+def _call_img(name, n_front, imgs, *args):
+    """The export `name`, or - the filter image(s) `imgs` given - its twin `name`_img, which takes the image pointer(s) right behind
+    the filter pointer(s) that close the first n_front arguments (the twins are bit-identical, and reject a NULL image)."""
+    if imgs[0] is not None:
+        name, args = name + "_img", args[:n_front] + tuple(L.ptr(i) for i in imgs) + args[n_front:]
+    L.check(getattr(L.load(), name)(*args, L.stream_ptr()), name)
+
+
+def _filter_grad(ws, dw, n_elem, call):
+    """One filter gradient, reduced now or deferred: call(dw_ptr, n_slabs_ref) performs the ABI call, which leaves partial-sum slabs
+    in ws and either finishes dw itself or - inside a fused.DeferredWgrads (the whole-model step: all slab reductions in one launch at
+    the end of the backward) - reports the slab count for the pending list."""
+    pending = fused.active_wgrads()
+    if pending is None:
+        call(L.ptr(dw), None)
+        return
+    ns = ctypes.c_int(0)
+    call(None, ctypes.byref(ns))
+    pending.add(ws, dw, ns.value, n_elem)
+
+
+def _conv_stats(C, n_parts, lazy, device):
+    """The by-products a float-family convolution's apply_with_stats hands to `apply` and then hangs on the output as
+    `y._alignq_bn_part`: the epilogue's partials (filled by the forward launch) and, where the node's backward will run, its link"""
+    return fused.ConvStats(torch.empty(C, n_parts, 2, dtype=torch.float32, device=device), n_parts, lazy,
+                           fused.LazyLink() if lazy else None)
 
 
 class QConv3x3Fn(torch.autograd.Function):
@@ -586,30 +619,19 @@ class QConv3x3Fn(torch.autograd.Function):
     instead of by a separate accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, tap=False, bn_stats=False, xbins=None, a_bit=0, img=None):
+    def forward(ctx, x, w, w_bit, tap=False, _unused=False, xbins=None, a_bit=0, img=None, part=None, link=None):
         """img: the filter's pre-packed bf16 images (weight_quantize_fn.take_image; a uint8 tensor written by the quantiser's launch
         from this w): forward and data gradient read them in place of w (alignq_conv3x3_nhwc_img, bit-identical).
-        bn_stats=True: the kernel's epilogue also leaves per-workgroup per-channel {sum y, sum y^2}; they are attached to
-        the output as `y._alignq_bn_part = (float tensor [C, parts, 2], parts)` for fused.bn_site, which then skips its own
-        statistics pass over y.
+        part / link (apply_with_stats): the kernel's epilogue also leaves per-workgroup per-channel {sum y, sum y^2} in `part`
+        (float [C, parts, 2]) for fused.bn_site, which then skips its own statistics pass over y and hands its lazy gradient back
+        through `link`.  (_unused keeps the positions behind it for callers that pass them by position.)
         xbins (N2): x is only a HANDLE (fused.packed_handle: shape and autograd edge, no data); the activation is read from its
         int8 / int16 level indices `xbins` (a_bit-bit ADMM-formula quantiser, ReLU already applied), forward and filter gradient."""
         B, C, H, W = x.shape
-        lib = L.load()
-        dev = w.device
-        y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        part, n_parts = None, 0
-        if bn_stats:
-            n_parts = lib.alignq_conv3x3_bn_parts(B, H, W, C)
-            part = torch.empty(C, n_parts, 2, dtype=torch.float32, device=dev) if n_parts > 0 else None
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
         xb = xbins.element_size() if xbins is not None else 0
-        if img is not None:
-            L.check(lib.alignq_conv3x3_nhwc_img(None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(img), L.ptr(y), B, H, W, C,
-                                                int(w_bit), 0, None, L.ptr(part), L.ptr(xbins), xb, int(a_bit), L.stream_ptr()),
-                    "alignq_conv3x3_nhwc_img")
-        else:
-            L.check(lib.alignq_conv3x3_nhwc(None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, int(w_bit), 0,
-                                            None, L.ptr(part), L.ptr(xbins), xb, int(a_bit), L.stream_ptr()), "alignq_conv3x3_nhwc")
+        _call_img("alignq_conv3x3_nhwc", 2, (img,), None if xbins is not None else L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, C, int(w_bit),
+                  0, None, L.ptr(part), L.ptr(xbins), xb, int(a_bit))
         if xbins is not None:
             ctx.save_for_backward(xbins, w)
         else:
@@ -618,16 +640,7 @@ class QConv3x3Fn(torch.autograd.Function):
         ctx.packed = (xbins is not None, int(a_bit), (B, C, H, W))
         ctx.w_bit = int(w_bit)
         ctx.tap = bool(tap)
-        ctx.link = None
-        if part is not None:
-            # third field: this producer's backward accepts a lazy BN gradient (1), and reduces the site backward's per-tile
-            # sums itself when both of its gradients are needed (2: the fused alignq_conv3x3_nhwc_bwd); fourth: the link
-            # through which the BN site's backward hands that gradient's record to THIS node's backward
-            if x.requires_grad or w.requires_grad:
-                ctx.link = fused.LazyLink()
-                L.MB.conv3x3 = (part, n_parts, 2 if (x.requires_grad and w.requires_grad) else 1, ctx.link)
-            else:       # this node's backward never runs: the BN site must finish its own input gradient
-                L.MB.conv3x3 = (part, n_parts)
+        ctx.link = link
         if tap:
             ctx.set_materialize_grads(False)
             return y, x.view_as(x)
@@ -635,26 +648,28 @@ class QConv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def apply_with_stats(x, w, w_bit, tap=False, xbins=None, a_bit=0, img=None):
-        """apply(...) with bn_stats=True; attaches the partial statistics to the returned y (a plain python attribute)."""
-        # the partials are created inside forward; fetch them through a one-slot mailbox (autograd hides ctx from callers)
-        L.MB.conv3x3 = None
-        out = QConv3x3Fn.apply(x, w, w_bit, tap, True, xbins, a_bit, img)
-        y = out[0] if tap else out
-        if L.MB.conv3x3 is not None:
-            y._alignq_bn_part = L.MB.conv3x3
-            L.MB.conv3x3 = None
+        """apply(...) whose forward also leaves the batch-norm partials; they ride on the returned y as `y._alignq_bn_part`
+        (fused.ConvStats, a plain python attribute).  lazy: this node's backward accepts a lazy BN gradient (1) and, when both of its
+        gradients are needed, reduces the site backward's per-tile sums itself (2: the fused alignq_conv3x3_nhwc_bwd)."""
+        B, C, H, W = x.shape
+        n_parts = L.load().alignq_conv3x3_bn_parts(B, H, W, C)
+        if n_parts <= 0:
+            return QConv3x3Fn.apply(x, w, w_bit, tap, False, xbins, a_bit, img)
+        stats = _conv_stats(C, n_parts, 2 if (x.requires_grad and w.requires_grad) else int(x.requires_grad or w.requires_grad),
+                            w.device)
+        out = QConv3x3Fn.apply(x, w, w_bit, tap, False, xbins, a_bit, img, stats.part, stats.link)
+        (out[0] if tap else out)._alignq_bn_part = stats
         return out
-
 
     @staticmethod
     def backward(ctx, gy, gtap=None):
         x, w = ctx.saved_tensors
         packed, a_bit, (B, C, H, W) = ctx.packed
-        none7 = (None,) * 6
+        nones = (None,) * 8
         img = ctx.img
         if gy is None:                     # only the shortcut alias was used downstream
-            return (gtap, None) + none7
-        lazy = fused.take_lazy_dz(ctx.link, gy)      # (g, z, ab, save, ktot): gy is the gradient w.r.t. the folded BN's OUTPUT
+            return (gtap, None) + nones
+        lazy = fused.take_lazy_dz(ctx.link, gy)      # a record: gy is the gradient w.r.t. the folded BN's OUTPUT
         dev = w.device
         cl = torch.channels_last
 
@@ -676,62 +691,31 @@ class QConv3x3Fn(torch.autograd.Function):
             dx, dw = new_x(), torch.empty_like(w)
             ws = _ws(lib.alignq_conv3x3_wgrad_ws_bytes(C), dev)
             ns = ctypes.c_int(0)
-            bz, bab, bsave, bk, bpart, bdg, bdb = lazy[1:8] if lazy is not None else (None,) * 7
             # filler role: this launch also finishes slab reductions of convolutions whose backward already ran
             fill = pending.take(C)
             nf = len(fill)
-            tail = (B, H, W, C, ctx.w_bit, ctypes.byref(ns), L.ptr(add), L.ptr(bz),
-                    L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart) if bk is None else None, L.ptr(bdg), L.ptr(bdb), xbp, xbb, a_bit,
-                    nf, L.ptr_array([f[0] for f in fill]) if nf else None, L.ptr_array([f[1] for f in fill]) if nf else None,
-                    (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
-                    (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None, L.stream_ptr())
-            if img is not None:
-                L.check(lib.alignq_conv3x3_nhwc_bwd_fill_img(xp, L.ptr(gy), L.ptr(w), L.ptr(img), L.ptr(dx), L.ptr(ws), *tail),
-                        "alignq_conv3x3_nhwc_bwd_fill_img")
-            else:
-                L.check(lib.alignq_conv3x3_nhwc_bwd_fill(xp, L.ptr(gy), L.ptr(w), L.ptr(dx), L.ptr(ws), *tail),
-                        "alignq_conv3x3_nhwc_bwd_fill")
+            _call_img("alignq_conv3x3_nhwc_bwd_fill", 3, (img,), xp, L.ptr(gy), L.ptr(w), L.ptr(dx), L.ptr(ws), B, H, W, C, ctx.w_bit,
+                      ctypes.byref(ns), L.ptr(add), *[L.ptr(t) for t in lazy.operands()], xbp, xbb, a_bit,
+                      nf, L.ptr_array([f[0] for f in fill]) if nf else None, L.ptr_array([f[1] for f in fill]) if nf else None,
+                      (ctypes.c_int * nf)(*[f[2] for f in fill]) if nf else None,
+                      (ctypes.c_int * nf)(*[f[3] for f in fill]) if nf else None)
             pending.add(ws, dw, ns.value, 9 * C * C)
-            return (dx, dw) + none7
-        if lazy is not None:               # not the fused path after all: finish the batch-norm input gradient here
-            bz, bab, bsave, bk = _lazy_fields(lazy, True, B, C, H * W, dev)[:4]
+            return (dx, dw) + nones
+        if lazy is not fused.NO_LAZY_BN:   # not the fused path after all: finish the batch-norm input gradient here
+            bz, bab, bsave, bk = lazy.operands(True, B, C, H * W)[:4]
             shp = (1, C, 1, 1)
             gy = bab[0].view(shp) * (gy - bk[0].view(shp) - (bz - bsave[0].view(shp)) * bsave[1].view(shp) * bk[1].view(shp))
             gy = gy.contiguous(memory_format=cl)
         if ctx.needs_input_grad[0]:
             dx = new_x()
-            if img is not None:
-                L.check(lib.alignq_conv3x3_nhwc_img(L.ptr(gy), L.ptr(w), L.ptr(img), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add),
-                                                    None, None, 0, 0, L.stream_ptr()), "alignq_conv3x3_nhwc_img")
-            else:
-                L.check(lib.alignq_conv3x3_nhwc(L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add), None, None, 0,
-                                                0, L.stream_ptr()), "alignq_conv3x3_nhwc")
+            _call_img("alignq_conv3x3_nhwc", 2, (img,), L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, C, ctx.w_bit, 1, L.ptr(add), None,
+                      None, 0, 0)
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)          # channels-last [C,3,3,C] storage like w
             ws = _ws(lib.alignq_conv3x3_wgrad_ws_bytes(C), dev)
-            if pending is not None:           # whole-model step: all filter-gradient reductions in one launch at the end
-                ns = ctypes.c_int(0)
-                L.check(lib.alignq_conv3x3_nhwc_wgrad(xp, L.ptr(gy), None, L.ptr(ws), B, H, W, C, ctypes.byref(ns), xbp, xbb, a_bit,
-                                                      L.stream_ptr()), "alignq_conv3x3_nhwc_wgrad")
-                pending.add(ws, dw, ns.value, 9 * C * C)
-            else:
-                L.check(lib.alignq_conv3x3_nhwc_wgrad(xp, L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, C, None, xbp, xbb, a_bit,
-                                                      L.stream_ptr()), "alignq_conv3x3_nhwc_wgrad")
-        return (dx, dw) + none7
-
-
-def _lazy_fields(lazy, need_totals_now, B, C, HW, device):
-    """(z, ab, save, ktot, part, dgamma, dbeta) of a lazy batch-norm record (fused.post_lazy_dz); when the record carries the
-    site backward's per-tile sums instead of finished totals and the caller's kernels cannot publish the parameter gradients
-    (need_totals_now), the totals are formed here (alignq_bn_bwd_totals)."""
-    if lazy is None:
-        return (None,) * 7
-    bz, bab, bsave, bk, bpart, bdg, bdb = lazy[1:8]
-    if bk is None and need_totals_now:
-        bk = torch.empty(2, C, dtype=torch.float32, device=device)
-        L.check(L.load().alignq_bn_bwd_totals(L.ptr(bpart), B, C, HW, L.ptr(bk), L.ptr(bdg), L.ptr(bdb), L.stream_ptr()),
-                "alignq_bn_bwd_totals")
-    return bz, bab, bsave, bk, (bpart if bk is None else None), bdg, bdb
+            _filter_grad(ws, dw, 9 * C * C, lambda dwp, nsp: L.check(lib.alignq_conv3x3_nhwc_wgrad(
+                xp, L.ptr(gy), dwp, L.ptr(ws), B, H, W, C, nsp, xbp, xbb, a_bit, L.stream_ptr()), "alignq_conv3x3_nhwc_wgrad"))
+        return (dx, dw) + nones
 
 
 def qconv_gen_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
@@ -763,30 +747,19 @@ class QConvGenFn(torch.autograd.Function):
     is added in this data-gradient kernel's epilogue instead of by a separate accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, padding, tap=False, img=None):
-        """img: the filter's pre-packed bf16 images (as QConv3x3Fn's), read by the forward and the data gradient."""
+    def forward(ctx, x, w, w_bit, padding, tap=False, img=None, part=None, link=None):
+        """img: the filter's pre-packed bf16 images (as QConv3x3Fn's), read by the forward and the data gradient.
+        part / link (apply_with_stats): the partials the launch fills and the lazy-gradient link, as QConv3x3Fn's."""
         B, CIN, H, W = x.shape
         COUT, ks = w.shape[0], w.shape[2]
-        lib = L.load()
+        if part is None:                   # a bare apply(): the launch leaves its partials all the same
+            part = _conv_stats(COUT, L.load().alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2), 0, x.device).part
         y = torch.empty((B, COUT, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        n_parts = lib.alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2)
-        part = torch.empty(COUT, n_parts, 2, dtype=torch.float32, device=x.device)
-        if img is not None:
-            L.check(lib.alignq_conv_gen_nhwc_fwd_img(L.ptr(x), L.ptr(w), L.ptr(img), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit),
-                                                     L.ptr(part), L.stream_ptr()), "alignq_conv_gen_nhwc_fwd_img")
-        else:
-            L.check(lib.alignq_conv_gen_nhwc_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit), L.ptr(part),
-                                                 L.stream_ptr()), "alignq_conv_gen_nhwc_fwd")
+        _call_img("alignq_conv_gen_nhwc_fwd", 2, (img,), L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, CIN, COUT, ks, 2, int(w_bit), L.ptr(part))
         ctx.save_for_backward(x, w)
         ctx.img = img
         ctx.w_bit = int(w_bit)
-        # 2: the data-gradient kernel reduces the site backward's per-tile sums and publishes the BN parameter gradients
-        ctx.link = None
-        if x.requires_grad or w.requires_grad:
-            ctx.link = fused.LazyLink()
-            L.MB.conv3x3 = (part, n_parts, 2 if x.requires_grad else 1, ctx.link)
-        else:
-            L.MB.conv3x3 = (part, n_parts)
+        ctx.link = link
         if tap:
             ctx.set_materialize_grads(False)
             return y, x.view_as(x)
@@ -796,51 +769,37 @@ class QConvGenFn(torch.autograd.Function):
     def backward(ctx, gy, gtap=None):
         x, w = ctx.saved_tensors
         if gy is None:                     # only the alias was used downstream
-            return gtap, None, None, None, None, None
+            return (gtap,) + (None,) * 7
         add = None if gtap is None else L.like_layout(gtap, x)
-        lazy = fused.take_lazy_dz(ctx.link, gy)      # (g, z, ab, save, ktot): gy is the gradient w.r.t. the folded BN's OUTPUT
+        lazy = fused.take_lazy_dz(ctx.link, gy)      # a record: gy is the gradient w.r.t. the folded BN's OUTPUT
         gy = gy.contiguous(memory_format=torch.channels_last)
         B, CIN, H, W = x.shape
         COUT, ks = w.shape[0], w.shape[2]
-        bz, bab, bsave, bk, bpart, bdg, bdb = _lazy_fields(lazy, not ctx.needs_input_grad[0], B, COUT, (H // 2) * (W // 2),
-                                                           x.device)
+        bn = [L.ptr(t) for t in lazy.operands(not ctx.needs_input_grad[0], B, COUT, (H // 2) * (W // 2))]
         lib = L.load()
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            tail = (B, H, W, CIN, COUT, ks, 2, ctx.w_bit, L.ptr(add), L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
-                    L.ptr(bdg), L.ptr(bdb), L.stream_ptr())
-            if ctx.img is not None:
-                L.check(lib.alignq_conv_gen_nhwc_dgrad_img(L.ptr(gy), L.ptr(w), L.ptr(ctx.img), L.ptr(dx), *tail),
-                        "alignq_conv_gen_nhwc_dgrad_img")
-            else:
-                L.check(lib.alignq_conv_gen_nhwc_dgrad(L.ptr(gy), L.ptr(w), L.ptr(dx), *tail), "alignq_conv_gen_nhwc_dgrad")
+            _call_img("alignq_conv_gen_nhwc_dgrad", 2, (ctx.img,), L.ptr(gy), L.ptr(w), L.ptr(dx), B, H, W, CIN, COUT, ks, 2, ctx.w_bit,
+                      L.ptr(add), *bn)
         elif add is not None:
             dx = add
         if ctx.needs_input_grad[1]:        # split-bf16 MFMA, deterministic slabs
             dw = torch.empty_like(w)
             ws = _ws(lib.alignq_conv_gen_wgrad_ws_bytes(CIN, COUT, ks), x.device)
-            pending = fused.active_wgrads()
-            if pending is not None:
-                ns = ctypes.c_int(0)
-                L.check(lib.alignq_conv_gen_nhwc_wgrad(L.ptr(x), L.ptr(gy), None, L.ptr(ws), B, H, W, CIN, COUT, ks, 2,
-                                                       ctypes.byref(ns), L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk),
-                                                       L.ptr(bpart), L.stream_ptr()), "alignq_conv_gen_nhwc_wgrad")
-                pending.add(ws, dw, ns.value, ks * ks * CIN * COUT)
-            else:
-                L.check(lib.alignq_conv_gen_nhwc_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, CIN, COUT, ks, 2,
-                                                       None, L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
-                                                       L.stream_ptr()), "alignq_conv_gen_nhwc_wgrad")
-        return dx, dw, None, None, None, None
+            _filter_grad(ws, dw, ks * ks * CIN * COUT, lambda dwp, nsp: L.check(lib.alignq_conv_gen_nhwc_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, CIN, COUT, ks, 2, nsp, *bn[:5], L.stream_ptr()),
+                "alignq_conv_gen_nhwc_wgrad"))
+        return (dx, dw) + (None,) * 6
 
     @staticmethod
     def apply_with_stats(x, w, w_bit, padding, tap=False, img=None):
-        L.MB.conv3x3 = None
-        out = QConvGenFn.apply(x, w, w_bit, padding, tap, img)
-        y = out[0] if tap else out
-        if L.MB.conv3x3 is not None:
-            y._alignq_bn_part = L.MB.conv3x3
-            L.MB.conv3x3 = None
+        """lazy 2: the data-gradient kernel reduces the site backward's per-tile sums and publishes the BN parameter gradients"""
+        B, CIN, H, W = x.shape
+        n_parts = L.load().alignq_conv_gen_bn_parts(B, H, W, CIN, w.shape[0], w.shape[2], 2)
+        stats = _conv_stats(w.shape[0], n_parts, 2 if x.requires_grad else int(w.requires_grad), x.device)
+        out = QConvGenFn.apply(x, w, w_bit, padding, tap, img, stats.part, stats.link)
+        (out[0] if tap else out)._alignq_bn_part = stats
         return out
 
 
@@ -850,36 +809,26 @@ class QTransitionFn(torch.autograd.Function):
     forward and four backward launches.  Both outputs carry their batch-norm partial statistics and lazy-gradient links like
     QConvGenFn's; values equal the separate launches'."""
 
-
     @staticmethod
-    def forward(ctx, x, w3, w1, w_bit, img3=None, img1=None):
-        """img3 / img1: both filters' pre-packed bf16 images (as QConv3x3Fn's; both or neither)."""
+    def forward(ctx, x, w3, w1, w_bit, img3=None, img1=None, part3=None, part1=None, link3=None, link1=None):
+        """img3 / img1: both filters' pre-packed bf16 images (as QConv3x3Fn's; both or neither).  part3 / part1 / link3 / link1
+        (apply_with_stats): both outputs' partials and lazy-gradient links, as QConvGenFn's."""
         if img3 is None or img1 is None:
             img3 = img1 = None
         B, CIN, H, W = x.shape
         COUT = w3.shape[0]
-        lib = L.load()
+        if part3 is None or part1 is None:       # a bare apply(): the launch leaves its partials all the same
+            part3, part1 = [_conv_stats(COUT, L.load().alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2), 0, x.device).part
+                            for ks in (3, 1)]
         cl = torch.channels_last
         y3 = torch.empty((B, COUT, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=cl)
         y1 = torch.empty((B, COUT, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=cl)
-        n3 = lib.alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, 3, 2)
-        n1 = lib.alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, 1, 2)
-        part3 = torch.empty(COUT, n3, 2, dtype=torch.float32, device=x.device)
-        part1 = torch.empty(COUT, n1, 2, dtype=torch.float32, device=x.device)
-        if img3 is not None:
-            L.check(lib.alignq_transition_nhwc_fwd_img(L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(img3), L.ptr(img1), L.ptr(y3), L.ptr(y1),
-                                                       B, H, W, CIN, COUT, int(w_bit), L.ptr(part3), L.ptr(part1), L.stream_ptr()),
-                    "alignq_transition_nhwc_fwd_img")
-        else:
-            L.check(lib.alignq_transition_nhwc_fwd(L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(y3), L.ptr(y1), B, H, W, CIN, COUT,
-                                                   int(w_bit), L.ptr(part3), L.ptr(part1), L.stream_ptr()),
-                    "alignq_transition_nhwc_fwd")
+        _call_img("alignq_transition_nhwc_fwd", 3, (img3, img1), L.ptr(x), L.ptr(w3), L.ptr(w1), L.ptr(y3), L.ptr(y1), B, H, W, CIN,
+                  COUT, int(w_bit), L.ptr(part3), L.ptr(part1))
         ctx.save_for_backward(x, w3, w1)
         ctx.imgs = (img3, img1)
         ctx.w_bit = int(w_bit)
-        ctx.link3, ctx.link1 = fused.LazyLink(), fused.LazyLink()
-        # mode 2: the data-gradient role reduces the site backward's per-tile sums and publishes the BN parameter gradients
-        L.MB.transition = ((part3, n3, 2, ctx.link3), (part1, n1, 2, ctx.link1))
+        ctx.link3, ctx.link1 = link3, link1
         return y3, y1
 
     @staticmethod
@@ -891,24 +840,16 @@ class QTransitionFn(torch.autograd.Function):
         gy3, gy1 = gy3.contiguous(memory_format=cl), gy1.contiguous(memory_format=cl)
         B, CIN, H, W = x.shape
         COUT = w3.shape[0]
-        HWo = (H // 2) * (W // 2)
-        f3 = _lazy_fields(lazy3, False, B, COUT, HWo, x.device)
-        f1 = _lazy_fields(lazy1, False, B, COUT, HWo, x.device)
         lib = L.load()
         dx = torch.empty_like(x)
         dw3, dw1 = torch.empty_like(w3), torch.empty_like(w1)
         ws3 = _ws(lib.alignq_conv_gen_wgrad_ws_bytes(CIN, COUT, 3), x.device)
         ws1 = _ws(lib.alignq_conv_gen_wgrad_ws_bytes(CIN, COUT, 1), x.device)
         ns3, ns1 = ctypes.c_int(0), ctypes.c_int(0)
-        tail = (L.ptr(dx), L.ptr(ws3), L.ptr(ws1), B, H, W, CIN, COUT, ctx.w_bit, ctypes.byref(ns3), ctypes.byref(ns1), None,
-                *[L.ptr(t) for t in f3], *[L.ptr(t) for t in f1], L.stream_ptr())
-        img3, img1 = ctx.imgs
-        if img3 is not None:
-            L.check(lib.alignq_transition_nhwc_bwd_img(L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), L.ptr(img3),
-                                                       L.ptr(img1), *tail), "alignq_transition_nhwc_bwd_img")
-        else:
-            L.check(lib.alignq_transition_nhwc_bwd(L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), *tail),
-                    "alignq_transition_nhwc_bwd")
+        _call_img("alignq_transition_nhwc_bwd", 5, ctx.imgs, L.ptr(x), L.ptr(gy3), L.ptr(gy1), L.ptr(w3), L.ptr(w1), L.ptr(dx),
+                  L.ptr(ws3), L.ptr(ws1), B, H, W, CIN, COUT, ctx.w_bit, ctypes.byref(ns3), ctypes.byref(ns1), None,
+                  *[L.ptr(t) for t in lazy3.operands() + lazy1.operands()])
+        # the two filters' slabs: with the step's closing reduction, or reduced here in one launch
         pending = fused.active_wgrads()
         if pending is not None:
             pending.add(ws3, dw3, ns3.value, 9 * CIN * COUT)
@@ -917,15 +858,17 @@ class QTransitionFn(torch.autograd.Function):
             L.check(lib.alignq_conv3x3_wgrad_reduce_multi(
                 2, L.ptr_array([ws3, ws1]), L.ptr_array([dw3, dw1]), (ctypes.c_int * 2)(ns3.value, ns1.value),
                 (ctypes.c_int * 2)(9 * CIN * COUT, CIN * COUT), L.stream_ptr()), "alignq_conv3x3_wgrad_reduce_multi")
-        return dx, dw3, dw1, None, None, None
+        return (dx, dw3, dw1) + (None,) * 7
 
     @staticmethod
     def apply_with_stats(x, w3, w1, w_bit, img3=None, img1=None):
-        L.MB.transition = None
-        y3, y1 = QTransitionFn.apply(x, w3, w1, w_bit, img3, img1)
-        if L.MB.transition is not None:
-            y3._alignq_bn_part, y1._alignq_bn_part = L.MB.transition
-            L.MB.transition = None
+        """lazy 2 (transition_supported: x and both filters need gradients): the data-gradient role reduces the site backward's
+        per-tile sums and publishes the BN parameter gradients"""
+        B, CIN, H, W = x.shape
+        COUT = w3.shape[0]
+        s3, s1 = [_conv_stats(COUT, L.load().alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2), 2, x.device) for ks in (3, 1)]
+        y3, y1 = QTransitionFn.apply(x, w3, w1, w_bit, img3, img1, s3.part, s1.part, s3.link, s1.link)
+        y3._alignq_bn_part, y1._alignq_bn_part = s3, s1
         return y3, y1
 
 
@@ -941,23 +884,30 @@ def transition_supported(conv3, conv1, x, w3, w1) -> bool:
             and qconv_gen_supported(*a1))
 
 
-def qconv_gemm_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
-    """The Conv2d_Q convolutions alignq_qconv_* take (the ResNet-50 / Office-31 shapes of BASELINE config 5): channels-last fp32,
-    C_in and C_out multiples of 64, 1x1 (padding 0) or 3x3 (padding 1), stride 1 or 2, <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or tuple(dilation) != (1, 1):
+def qconv_gemm_shape_supported(shape, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The Conv2d_Q convolutions alignq_qconv_* take (the ResNet-50 / Office-31 shapes of BASELINE config 5), for an input given by its
+    SHAPE only (a packed handle, fused.packed_handle: the values live in int16 level indices laid out channels-last): C_in and C_out
+    multiples of 64, 1x1 (padding 0) or 3x3 (padding 1), stride 1 or 2, <= 8-bit quantised filter."""
+    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or tuple(dilation) != (1, 1) or len(shape) != 4:
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32 and w.is_cuda):
+    if not (w.dtype == torch.float32 and w.is_cuda):
         return False
-    B, CIN, H, W = x.shape
+    B, CIN, H, W = shape
     COUT, ks = w.shape[0], w.shape[2]
     if w.shape[1] != CIN or w.shape[3] != ks or ks not in (1, 3) or tuple(padding) != ((ks - 1) // 2,) * 2:
         return False
     if stride[0] != stride[1] or stride[0] not in (1, 2):
         return False
-    cl = torch.channels_last
-    if not (x.is_contiguous(memory_format=cl) and (ks == 1 or w.is_contiguous(memory_format=cl))):
+    if not (ks == 1 or w.is_contiguous(memory_format=torch.channels_last)):
         return False
     return bool(L.load().alignq_qconv_supported(B, H, W, CIN, COUT, ks, int(stride[0])))
+
+
+def qconv_gemm_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """qconv_gemm_shape_supported for a channels-last fp32 tensor."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return qconv_gemm_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
 
 
 def level_count(t):
@@ -977,34 +927,18 @@ def pack_filter_bins(weights, w_bit):
     return list(zip(bf, hf))
 
 
-def qconv_gemm_shape_supported(shape, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
-    """qconv_gemm_supported for an input given by its SHAPE only (a packed handle, fused.packed_handle: the values live in int16
-    level indices laid out channels-last)."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or tuple(dilation) != (1, 1) or len(shape) != 4:
-        return False
-    if not (w.dtype == torch.float32 and w.is_cuda):
-        return False
-    B, CIN, H, W = shape
-    COUT, ks = w.shape[0], w.shape[2]
-    if w.shape[1] != CIN or w.shape[3] != ks or ks not in (1, 3) or tuple(padding) != ((ks - 1) // 2,) * 2:
-        return False
-    if stride[0] != stride[1] or stride[0] not in (1, 2):
-        return False
-    if not (ks == 1 or w.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    return bool(L.load().alignq_qconv_supported(B, H, W, CIN, COUT, ks, int(stride[0])))
-
-
 class QConvGemmFn(torch.autograd.Function):
     """F.conv2d(input, weight_q, None, stride, padding) of Conv2d_Q.forward (cdf_alignment_admm/dann_office/model/quantization.py:
     164-181) at the ResNet-50 shapes on alignq_qconv_fwd / _dgrad / _wgrad (csrc/qgemm_kernels.hip): exact products on the bf16 /
     f16 matrix cores.  x_levels: see level_count (0.0: a general fp32 input).  bins: (bf16, f16) bit patterns of the filter's
     integer bins from pack_filter_bins (None: packed here, one small launch).  xbins (N2): x is only a HANDLE (fused.packed_handle:
     shape and autograd edge); the activation is read from its int16 level indices `xbins`, forward and filter gradient.  The filter
-    gradient's slab reduction is deferred to fused.DeferredWgrads when such a context is active."""
+    gradient's slab reduction is deferred to fused.DeferredWgrads when such a context is active.  part (apply_with_stats): the
+    epilogue's batch-norm partials, double [groups, parts, C_out, 2], filled by the forward launch (_unused keeps the positions
+    behind it for callers that pass them by position)."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, stride, x_levels=0.0, groups=1, bn_stats=False, bins=None, xbins=None):
+    def forward(ctx, x, w, w_bit, stride, x_levels=0.0, groups=1, _unused=False, bins=None, xbins=None, part=None):
         B, CIN, H, W = x.shape
         COUT, ks = w.shape[0], w.shape[2]
         s = int(stride)
@@ -1016,28 +950,22 @@ class QConvGemmFn(torch.autograd.Function):
                                       and xbins.is_contiguous(memory_format=torch.channels_last)):
             raise RuntimeError("QConvGemmFn: xbins must be the channels-last int16 level indices of a level tensor of x's shape")
         y = torch.empty((B, COUT, Ho, Wo), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
-        part = None
-        if bn_stats:
-            n_parts = lib.alignq_qconv_bn_parts(B, H, W, CIN, COUT, ks, s, int(groups), float(x_levels))
-            part = torch.empty(int(groups), n_parts, COUT, 2, dtype=torch.float64, device=w.device)
-            L.MB.gemm = (part, n_parts)
         L.check(lib.alignq_qconv_fwd(L.ptr(xbins if xbins is not None else x), L.ptr(bins[1] if x_levels else bins[0]), L.ptr(y), B, H, W,
                                      CIN, COUT, ks, s, int(w_bit), float(x_levels), 2 if xbins is not None else 0,
-                                     int(groups if bn_stats else 1), L.ptr(part), L.stream_ptr()), "alignq_qconv_fwd")
+                                     int(groups if part is not None else 1), L.ptr(part), L.stream_ptr()), "alignq_qconv_fwd")
         ctx.save_for_backward(xbins if xbins is not None else x, w, bins[0])
         ctx.cfg = (int(w_bit), s, float(x_levels), ks, xbins is not None, (B, CIN, H, W))
         return y
 
-
     @staticmethod
     def apply_with_stats(x, w, w_bit, stride, x_levels=0.0, groups=1, bins=None, xbins=None):
-        """apply(...) that also leaves the batch-norm partial statistics of the output on it: y._alignq_bnq_part =
-        (double tensor [groups, parts, C_out, 2], parts, groups) for fused.bn_act_relu / bn_only / bn_site_res_relu."""
-        L.MB.gemm = None
-        y = QConvGemmFn.apply(x, w, w_bit, stride, x_levels, groups, True, bins, xbins)
-        if L.MB.gemm is not None:
-            y._alignq_bnq_part = L.MB.gemm + (int(groups),)
-            L.MB.gemm = None
+        """apply(...) whose forward also leaves the batch-norm partial statistics of the output, per batch slice; they ride on y as
+        `y._alignq_bnq_part` (fused.ConvStatsQ) for fused.bn_act_relu / bn_only / bn_site_res_relu."""
+        B, CIN, H, W = x.shape
+        n_parts = L.load().alignq_qconv_bn_parts(B, H, W, CIN, w.shape[0], w.shape[2], int(stride), int(groups), float(x_levels))
+        part = torch.empty(int(groups), n_parts, w.shape[0], 2, dtype=torch.float64, device=w.device)
+        y = QConvGemmFn.apply(x, w, w_bit, stride, x_levels, groups, False, bins, xbins, part)
+        y._alignq_bnq_part = fused.ConvStatsQ(part, n_parts, int(groups))
         return y
 
     @staticmethod
@@ -1063,16 +991,9 @@ class QConvGemmFn(torch.autograd.Function):
             dw = torch.empty_like(w)
             ws = _ws(lib.alignq_qconv_wgrad_ws_bytes(B, H, W, CIN, COUT, ks, s), w.device)
             xb = 2 if packed else 0
-            pending = fused.active_wgrads()
-            if pending is not None:
-                ns = ctypes.c_int(0)
-                L.check(lib.alignq_qconv_wgrad(L.ptr(x), L.ptr(gy), None, L.ptr(ws), B, H, W, CIN, COUT, ks, s, x_levels, xb,
-                                               ctypes.byref(ns), L.stream_ptr()), "alignq_qconv_wgrad")
-                pending.add(ws, dw, ns.value, COUT * ks * ks * CIN)
-            else:
-                L.check(lib.alignq_qconv_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, CIN, COUT, ks, s, x_levels, xb, None,
-                                               L.stream_ptr()), "alignq_qconv_wgrad")
-        return dx, dw, None, None, None, None, None, None, None
+            _filter_grad(ws, dw, COUT * ks * ks * CIN, lambda dwp, nsp: L.check(lib.alignq_qconv_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, CIN, COUT, ks, s, x_levels, xb, nsp, L.stream_ptr()), "alignq_qconv_wgrad"))
+        return (dx, dw) + (None,) * 8
 
 
 def qconv_stem7_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
@@ -1093,23 +1014,18 @@ def qconv_stem7_supported(x, w, stride, padding, dilation, groups, bias, w_bit) 
 class QConvStem7Fn(torch.autograd.Function):
     """F.conv2d(image, weight_q, None, 2, 3) of the Office stem on alignq_qconv_stem7_fwd (csrc/qgemm_kernels.hip: the filter's integer
     bins times three exact bf16 terms of the image, gathered straight from global memory); batch-norm statistics of the output in
-    the epilogue (bn_stats).  The image needs no gradient; the filter gradient is alignq_qconv_stem7_wgrad's (six leading term pairs,
+    the epilogue (part and _unused: as QConvGemmFn's).  The image needs no gradient; the filter gradient is alignq_qconv_stem7_wgrad's (six leading term pairs,
     deterministic slabs; their reduction is deferred to fused.DeferredWgrads when such a context is active)."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, groups=1, bn_stats=False, bins=None):
+    def forward(ctx, x, w, w_bit, groups=1, _unused=False, bins=None, part=None):
         B, _, H, W = x.shape
         lib = L.load()
         if bins is None:
             bins = pack_filter_bins([w], w_bit)[0]
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty((B, 64, Ho, Wo), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
-        part = None
-        if bn_stats:
-            n_parts = lib.alignq_qconv_stem7_bn_parts(B, H, W, int(groups))
-            part = torch.empty(int(groups), n_parts, 64, 2, dtype=torch.float64, device=w.device)
-            L.MB.gemm = (part, n_parts)
-        L.check(lib.alignq_qconv_stem7_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B, H, W, int(w_bit), int(groups if bn_stats else 1),
+        L.check(lib.alignq_qconv_stem7_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B, H, W, int(w_bit), int(groups if part is not None else 1),
                                            L.ptr(part), L.stream_ptr()), "alignq_qconv_stem7_fwd")
         ctx.save_for_backward(x, w)
         return y
@@ -1117,11 +1033,11 @@ class QConvStem7Fn(torch.autograd.Function):
     @staticmethod
     def apply_with_stats(x, w, w_bit, groups=1, bins=None):
         """apply(...) that also leaves y._alignq_bnq_part (see QConvGemmFn.apply_with_stats)"""
-        L.MB.gemm = None
-        y = QConvStem7Fn.apply(x, w, w_bit, groups, True, bins)
-        if L.MB.gemm is not None:
-            y._alignq_bnq_part = L.MB.gemm + (int(groups),)
-            L.MB.gemm = None
+        B, _, H, W = x.shape
+        n_parts = L.load().alignq_qconv_stem7_bn_parts(B, H, W, int(groups))
+        part = torch.empty(int(groups), n_parts, 64, 2, dtype=torch.float64, device=w.device)
+        y = QConvStem7Fn.apply(x, w, w_bit, groups, False, bins, part)
+        y._alignq_bnq_part = fused.ConvStatsQ(part, n_parts, int(groups))
         return y
 
     @staticmethod
@@ -1135,16 +1051,9 @@ class QConvStem7Fn(torch.autograd.Function):
             lib = L.load()
             dw = torch.empty_like(w)
             ws = _ws(lib.alignq_qconv_stem7_wgrad_ws_bytes(B, H, W), w.device)
-            pending = fused.active_wgrads()
-            if pending is not None:         # the slab reduction rides in the step's closing reduction launch
-                ns = ctypes.c_int(0)
-                L.check(lib.alignq_qconv_stem7_wgrad(L.ptr(x), L.ptr(gy), None, L.ptr(ws), B, H, W, ctypes.byref(ns), L.stream_ptr()),
-                        "alignq_qconv_stem7_wgrad")
-                pending.add(ws, dw, ns.value, 64 * 147)
-            else:
-                L.check(lib.alignq_qconv_stem7_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, None, L.stream_ptr()),
-                        "alignq_qconv_stem7_wgrad")
-        return None, dw, None, None, None, None
+            _filter_grad(ws, dw, 64 * 147, lambda dwp, nsp: L.check(lib.alignq_qconv_stem7_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, nsp, L.stream_ptr()), "alignq_qconv_stem7_wgrad"))
+        return (None, dw) + (None,) * 5
 
 
 def qconv_stem_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
@@ -1166,22 +1075,17 @@ class QConvStemFn(torch.autograd.Function):
     """The stem convolution (model/resnet.py: conv0 = Conv2d_Q(3, 16, 3, 1, 1)) on alignq_conv_stem_nhwc_fwd / _wgrad."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit):
+    def forward(ctx, x, w, w_bit, part=None, link=None):
+        """part / link (apply_with_stats): the partials the launch fills and the lazy-gradient link, as QConv3x3Fn's."""
         B, _, H, W = x.shape
         lib = L.load()
+        if part is None:                   # a bare apply(): the launch leaves its partials all the same
+            part = _conv_stats(16, lib.alignq_conv_stem_bn_parts(B, H, W), 0, x.device).part
         y = torch.empty((B, 16, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        n_parts = lib.alignq_conv_stem_bn_parts(B, H, W)
-        part = torch.empty(16, n_parts, 2, dtype=torch.float32, device=x.device)
         L.check(lib.alignq_conv_stem_nhwc_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, H, W, int(w_bit), L.ptr(part), L.stream_ptr()),
                 "alignq_conv_stem_nhwc_fwd")
         ctx.save_for_backward(x, w)
-        # 2: the filter-gradient kernel (the stem's only gradient) reduces the site backward's per-tile sums itself
-        ctx.link = None
-        if w.requires_grad:
-            ctx.link = fused.LazyLink()
-            L.MB.conv3x3 = (part, n_parts, 2, ctx.link)
-        else:
-            L.MB.conv3x3 = (part, n_parts)
+        ctx.link = link
         return y
 
     @staticmethod
@@ -1190,32 +1094,23 @@ class QConvStemFn(torch.autograd.Function):
         lazy = fused.take_lazy_dz(ctx.link, gy)
         gy = gy.contiguous(memory_format=torch.channels_last)
         B, _, H, W = x.shape
-        bz, bab, bsave, bk, bpart, bdg, bdb = _lazy_fields(lazy, not ctx.needs_input_grad[1], B, 16, H * W, x.device)
+        bn = [L.ptr(t) for t in lazy.operands(not ctx.needs_input_grad[1], B, 16, H * W)]
         lib = L.load()
         dw = None
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
             ws = _ws(256 * 16 * 27 * 4, x.device)
-            pending = fused.active_wgrads()
-            if pending is not None:
-                ns = ctypes.c_int(0)
-                L.check(lib.alignq_conv_stem_nhwc_wgrad(L.ptr(x), L.ptr(gy), None, L.ptr(ws), B, H, W, ctypes.byref(ns),
-                                                        L.ptr(bz), L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart),
-                                                        L.ptr(bdg), L.ptr(bdb), L.stream_ptr()), "alignq_conv_stem_nhwc_wgrad")
-                pending.add(ws, dw, ns.value, 16 * 27)
-            else:
-                L.check(lib.alignq_conv_stem_nhwc_wgrad(L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(ws), B, H, W, None, L.ptr(bz),
-                                                        L.ptr(bab), L.ptr(bsave), L.ptr(bk), L.ptr(bpart), L.ptr(bdg),
-                                                        L.ptr(bdb), L.stream_ptr()), "alignq_conv_stem_nhwc_wgrad")
-        return None, dw, None
+            _filter_grad(ws, dw, 16 * 27, lambda dwp, nsp: L.check(lib.alignq_conv_stem_nhwc_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, nsp, *bn, L.stream_ptr()), "alignq_conv_stem_nhwc_wgrad"))
+        return None, dw, None, None, None
 
     @staticmethod
     def apply_with_stats(x, w, w_bit):
-        L.MB.conv3x3 = None
-        y = QConvStemFn.apply(x, w, w_bit)
-        if L.MB.conv3x3 is not None:
-            y._alignq_bn_part = L.MB.conv3x3
-            L.MB.conv3x3 = None
+        """lazy 2: the filter-gradient kernel (the stem's only gradient) reduces the site backward's per-tile sums itself"""
+        B, _, H, W = x.shape
+        stats = _conv_stats(16, L.load().alignq_conv_stem_bn_parts(B, H, W), 2 if w.requires_grad else 0, x.device)
+        y = QConvStemFn.apply(x, w, w_bit, stats.part, stats.link)
+        y._alignq_bn_part = stats
         return y
 
 

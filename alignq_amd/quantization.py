@@ -270,11 +270,9 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     # N2: the input is a packed handle (fused.bn_site(pack=True)): its values are int8 / int16 level
                     # indices; the 3x3 body convolution reads them directly, anything else gets the dequantised tensor
                     bins, a_bit = packed
-                    B_, C_, H_, W_ = input.shape
-                    if (getattr(self, "use_qconv", False) and self.bias is None and self.groups == 1 and weight_q.is_cuda
-                            and tuple(self.stride) == (1, 1) and tuple(self.padding) == (1, 1) and tuple(self.dilation) == (1, 1)
-                            and tuple(weight_q.shape) == (C_, C_, 3, 3) and (C_, W_) in ((16, 32), (32, 16), (64, 8)) and H_ % 8 == 0
-                            and 1 <= self.quantize_fn.w_bit <= 8 and weight_q.is_contiguous(memory_format=torch.channels_last)):
+                    if (getattr(self, "use_qconv", False) and weight_q.is_cuda
+                            and ops.qconv3x3_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
+                                                             self.groups, self.bias, self.quantize_fn.w_bit)):
                         return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit,
                                                                self.quantize_fn.take_image(weight_q))
                     if (getattr(self, "use_qconv", False) and bins.dtype == torch.int16 and ops.level_count(input)

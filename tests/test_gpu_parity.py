@@ -1012,7 +1012,7 @@ def test_conv_epilogue_bn_statistics_feed_the_fold(dev, B, C, H, k):
     (2) fused.bn_site consuming them (no statistics pass over y) gives the same site results as with its own statistics
     kernel: identical up to the float-vs-double rounding of the partial sums (tie-zone bin flips only)."""
     import alignq_amd.cdf_alignment_admm as A
-    from alignq_amd import config, ops
+    from alignq_amd import config, fused, ops
     from alignq_amd.fused import bn_site
     config.args.bitW = config.args.abitW = k
     torch.manual_seed(B + C)
@@ -1035,7 +1035,7 @@ def test_conv_epilogue_bn_statistics_feed_the_fold(dev, B, C, H, k):
         act = A.activation_quantize_fn(k, "second", admm)
         z = y.detach().clone(memory_format=cl).requires_grad_(True)
         if with_part:
-            z._alignq_bn_part = (part, n_parts)
+            z._alignq_bn_part = fused.ConvStats(part, n_parts)
         xq, loss = bn_site(bn, act, z, relu=True)
         (loss + (xq * gq).sum()).backward()
         outs.append(dict(xq=npy(xq), D=npy(admm.D), loss=float(loss.detach()), dz=npy(z.grad), rm=npy(bn.running_mean),
