@@ -1698,7 +1698,9 @@ int alignq_conv3x3_nhwc_img(const float* x, const float* wt, const void* w_img, 
 
 size_t alignq_conv3x3_wgrad_ws_bytes(int C) { return (size_t)256 * 9 * (size_t)C * C * sizeof(float); }
 
-// dW[co,ky,kx,ci] = sum_{b,h,w} dy[b,h,w,co] * x[b,h+ky-1,w+kx-1,ci]; plain fp32 (v_mfma_f32_*_f32), deterministic.
+// dW[co,ky,kx,ci] = sum_{b,h,w} dy[b,h,w,co] * x[b,h+ky-1,w+kx-1,ci]; split-bf16 (wgrad_body: three exact bf16 terms per
+// operand, the six (dy term, x term) pairs hh, hm, mh, hl, lh, mm on v_mfma_f32_16x16x32_bf16, fp32 accumulation; the dropped
+// ml, lm, ll are at most about 2^-26 of a product each), deterministic.
 // n_slabs_out == NULL: partial sums + reduction (two launches), dw is complete on return.
 // n_slabs_out != NULL: partial sums only; *n_slabs_out receives the number of slabs left in ws for
 // alignq_conv3x3_wgrad_reduce_multi.

@@ -405,8 +405,10 @@ int alignq_conv_stem_nhwc_wgrad(const float* x, const float* dy, float* dw, void
                                 const float* bn_z, const float* bn_ab, const float* bn_save, const float* bn_ktot,
                                 const float* bn_dx_part, float* bn_dgamma, float* bn_dbeta, void* stream);
 
-/* Filter gradient of the same convolution, dW [C,3,3,C] (channels-last weight storage) from x and dy: plain fp32 on the f32
- * MFMAs (products and accumulation bit-for-bit an fmaf chain), per-pixel-range partial sums in ws
+/* Filter gradient of the same convolution, dW [C,3,3,C] (channels-last weight storage) from x and dy: split-bf16 on
+ * v_mfma_f32_16x16x32_bf16.  Both operands are general fp32, so each is split exactly into three bf16 terms h + m + l and a
+ * product keeps six of the nine (dy term, x term) pairs - hh, hm, mh, hl, lh, mm - each exact in fp32, accumulated in fp32; the
+ * dropped ml, lm and ll are at most about 2^-26 of the product each.  Per-pixel-range partial sums in ws
  * (alignq_conv3x3_wgrad_ws_bytes(C)) reduced in fixed order by a second launch: deterministic, no zero-fill, no atomics.  */
 size_t alignq_conv3x3_wgrad_ws_bytes(int C);
 int alignq_conv3x3_nhwc_wgrad(const float* x, const float* dy, float* dw, void* ws, int B, int H, int W, int C,
