@@ -5,6 +5,11 @@
   (2) the golden vectors captured from the reference       -> bins exact outside the erf tie zone
       (|frac(t*n) - 1/2| < 1e-4), dequantised values and residuals within 1e-5;
   (3) size-independent properties at BASELINE.json's full sizes.
+
+The site tests here feed the ADMM loss's own dD, whose correlation gradient d(corr(t,t) - corr(x,x))/dx is smaller than the
+1e-5 they compare dx at: they check x_q, D, the loss and the straight-through term g * dt/dx.  The correlation gradient is
+checked BY VALUE, at the size of its own cancelling terms and in every launch form, in tests/test_gpu_site_corr_grad.py
+(reference and bar: tests/site_grad_oracle.py).
 """
 import numpy as np
 import pytest
