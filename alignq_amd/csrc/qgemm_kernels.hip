@@ -1196,7 +1196,9 @@ int launch_g(QG a, hipStream_t st) {
   // k units per workgroup (the parity-class form: 1 to 4 taps, 2.25 on average)
   const int units = KM == 2 ? a.CA / KBh : (KM == 1 ? 9 : (KM == 3 ? 2 : 1)) * (a.CA / BK);
   a.ksplit = (a.part && !a.bn_part) ? pick_ksplit(blocks, 256 * OCC, units) : 1;
-  if (KM == 3 && a.ksplit > a.CA / BK) a.ksplit = 1;          // (a one-tap class must have a k unit for every split)
+  // (a one-tap class must have a k unit for every split.  pick_ksplit only tries S with units / S >= 2 and units = 2 CA / BK here, so
+  // S <= CA / BK already: the guard states the requirement, no shape reaches it)
+  if (KM == 3 && a.ksplit > a.CA / BK) a.ksplit = 1;
   if (a.part && a.ksplit > a.part_splits) return ALIGNQ_EINVAL;   // (the workspace query and this launch disagree on the plan: never write past it)
   hipLaunchKernelGGL((qgemm_kernel<WN, TM, MODE, WTR, KM, SCATTER, OCC, XI>), dim3(blocks * a.ksplit), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
@@ -1211,7 +1213,8 @@ int launch_g(QG a, hipStream_t st) {
   return e == hipSuccess ? 0 : (int)e;
 }
 
-// Tile choice: the largest of 128x128, 64x128, 64x64 (pixels x channels) that still gives the chip >= `want` workgroups
+// Tile choice: the largest of 128x128, 64x128, 64x64 (pixels x channels) that still gives the chip >= `want` workgroups; 128x64
+// for an N that is no multiple of 128 when it gives >= 2 `want` (no ResNet-50 layer: N = 320 needs 52353 rows)
 // (rows = all groups' rows; alignq_qconv_bn_parts reports the row tiles per group of the same choice).  The halo form of a level
 // operand (64 channels per step) keeps to 64-row tiles: its image of 128 + 2 W + 2 rows would not fit the prefetch registers.
 constexpr int kWantBlocks = 1024;        // (round 5 sweep 512 / 768 / 1024 / 1536: forward + data gradient 4717 / 4651 / 4656 / 4733 us per iteration)
