@@ -20,6 +20,7 @@
 
 #include "../../include/alignq.h"
 #include "site_internal.h"
+#include "store_forms.h"
 #include "wgrad_reduce_body.h"
 
 namespace {
@@ -368,7 +369,7 @@ __device__ __forceinline__ void conv3x3_body(const float* __restrict__ x, const 
         const float4 r = *reinterpret_cast<const float4*>(add + o);
         v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
       }
-      *reinterpret_cast<float4*>(y + o) = v;
+      alignq_store::st16<alignq_store::kConvOut>(y + o, v);
       bs[0] += v.x; bs[1] += v.y; bs[2] += v.z; bs[3] += v.w;
       bq[0] += v.x * v.x; bq[1] += v.y * v.y; bq[2] += v.z * v.z; bq[3] += v.w * v.w;
     }
@@ -563,7 +564,7 @@ __device__ __forceinline__ void convgen_fwd_body(const float* __restrict__ x, co
     const int grow = row0 + r;
     if (grow < total_rows) {
       const float4 v = make_float4(acc[gi][0] / nlev, acc[gi][1] / nlev, acc[gi][2] / nlev, acc[gi][3] / nlev);
-      *reinterpret_cast<float4*>(y + ((int64_t)grow * WDO + c) * COUT + cog * 16 + 4 * q) = v;
+      alignq_store::st16<alignq_store::kConvOut>(y + ((int64_t)grow * WDO + c) * COUT + cog * 16 + 4 * q, v);
       bs[0] += v.x; bs[1] += v.y; bs[2] += v.z; bs[3] += v.w;
       bq[0] += v.x * v.x; bq[1] += v.y * v.y; bq[2] += v.z * v.z; bq[3] += v.w * v.w;
     }
@@ -818,7 +819,7 @@ __device__ __forceinline__ void dgrad_s2_body(const float* __restrict__ dy, cons
         const float4 a4 = *reinterpret_cast<const float4*>(add + o);
         out.x += a4.x; out.y += a4.y; out.z += a4.z; out.w += a4.w;
       }
-      *reinterpret_cast<float4*>(dx + o) = out;
+      alignq_store::st16<alignq_store::kConvOut>(dx + o, out);
     }
   }
 }
@@ -921,7 +922,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
     const int grow = row0 + p / 32;
     if (grow < total_rows) {
       const float4 v = make_float4(acc[0] / nlev, acc[1] / nlev, acc[2] / nlev, acc[3] / nlev);
-      *reinterpret_cast<float4*>(y + ((int64_t)grow * 32 + p % 32) * 16 + 4 * q) = v;
+      alignq_store::st16<alignq_store::kConvOut>(y + ((int64_t)grow * 32 + p % 32) * 16 + 4 * q, v);
       bs[0] += v.x; bs[1] += v.y; bs[2] += v.z; bs[3] += v.w;
       bq[0] += v.x * v.x; bq[1] += v.y * v.y; bq[2] += v.z * v.z; bq[3] += v.w * v.w;
     }
@@ -1339,8 +1340,9 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
           float v = acc[t][e];
 #pragma unroll
           for (int w2 = 0; w2 < 3; w2++) v += red[((w2 * NT + t) * 4 + e) * 64 + lane];
-          // non-temporal: the slab is read once, launches later; it must not displace dx (the next launch's operand) from the caches
-          __builtin_nontemporal_store(v, &slab[((int64_t)(bi * CB + 4 * (lane >> 4) + e) * NT + t) * CIN + bj * CB + (lane & 15)]);
+          // write-through (store_forms.h; the plain build: non-temporal): the slab is read once, launches later; it must not displace
+          // dx (the next launch's operand) from the caches, and its write-back must not hold up the next launch
+          alignq_store::st4<alignq_store::kConvWgradSlab, true>(&slab[((int64_t)(bi * CB + 4 * (lane >> 4) + e) * NT + t) * CIN + bj * CB + (lane & 15)], v);
         }
       }
     }
@@ -1349,7 +1351,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ x, const fl
     for (int t = 0; t < NT; t++)
 #pragma unroll
       for (int e = 0; e < 4; e++)
-        __builtin_nontemporal_store(acc[t][e], &slab[((int64_t)(bi * CB + cob * 16 + 4 * (lane >> 4) + e) * NT + t) * CIN + bj * CB + cib * 16 + (lane & 15)]);
+        alignq_store::st4<alignq_store::kConvWgradSlab, true>(&slab[((int64_t)(bi * CB + cob * 16 + 4 * (lane >> 4) + e) * NT + t) * CIN + bj * CB + cib * 16 + (lane & 15)], acc[t][e]);
   }
   STAMP(st_on, 51);
 }

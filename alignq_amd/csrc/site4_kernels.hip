@@ -20,6 +20,7 @@
 #include "alignq_math.h"
 #include "site_internal.h"
 #include "head_body.h"
+#include "store_forms.h"
 
 using namespace alignq;
 
@@ -633,7 +634,9 @@ __global__ __launch_bounds__(NTv, 4) void site_fwd4_kernel(const float* __restri
           q.x += rr.x; q.y += rr.y; q.z += rr.z; q.w += rr.w;
         }
         if (!kPlain && bn.relu) { q.x = fmaxf(q.x, 0.f); q.y = fmaxf(q.y, 0.f); q.z = fmaxf(q.z, 0.f); q.w = fmaxf(q.w, 0.f); }
-        if constexpr (kFull) {
+        if constexpr (FULLP) {            // the one-tile form's first-phase output: write-through (store_forms.h)
+          if (xq) alignq_store::st16<alignq_store::kSiteFwdEarly>(xq, 4u * off, q);
+        } else if constexpr (kFull) {
           if (xq) *reinterpret_cast<float4*>(reinterpret_cast<char*>(xq) + 4u * off) = q;
         } else {
           if (xq) st4(xq, off, col, F, ok, aligned, q);
@@ -854,11 +857,13 @@ __global__ __launch_bounds__(NTv, 4) void site_fwd4_kernel(const float* __restri
   // triangles two to a [32][33] block
   float* slab = slabs + (int64_t)bid * kSlab4Floats;
   float4* slab4 = reinterpret_cast<float4*>(slab);
+  constexpr bool kSlabWt = SINGLE && alignq_store::on(alignq_store::kSiteFwdSlab);   // the one-tile forms: write-through (store_forms.h)
   const float4* C4 = reinterpret_cast<const float4*>(C);
   for (int e = tid; e < kSlab4Off / 4; e += NTv) {
     const int t6 = e >> 8;                                      // C tiles 1, 2, 3, 5, 6, 8
     const int tl = t6 < 3 ? t6 + 1 : (t6 < 5 ? t6 + 2 : 8);
-    slab4[e] = C4[tl * 256 + (e & 255)];
+    if constexpr (kSlabWt) alignq_store::st16<alignq_store::kSiteFwdSlab>(slab, 16u * (unsigned)e, C4[tl * 256 + (e & 255)]);
+    else slab4[e] = C4[tl * 256 + (e & 255)];
   }
   for (int idx = tid; idx < kSlab4Packed; idx += NTv) {
     const int blk = idx / 1056, rem = idx - blk * 1056;
@@ -867,7 +872,8 @@ __global__ __launch_bounds__(NTv, 4) void site_fwd4_kernel(const float* __restri
     const int rr = second ? col : row, cc2 = second ? row : col - 1;
     const int d = 2 * blk + (second ? 1 : 0);
     const int tl = d == 0 ? 0 : (d == 1 ? 4 : (d == 2 ? 7 : 9));
-    slab[kSlab4Off + idx] = C[tl * 1024 + rr * 32 + cc2];
+    if constexpr (kSlabWt) alignq_store::st4<alignq_store::kSiteFwdSlab>(slab, 4u * (unsigned)(kSlab4Off + idx), C[tl * 1024 + rr * 32 + cc2]);
+    else slab[kSlab4Off + idx] = C[tl * 1024 + rr * 32 + cc2];
   }
   STAMP(5);
   BSTAMP(0, 1);
@@ -1596,7 +1602,7 @@ __global__ __launch_bounds__(TFv * 8, 2) void site_bwd4_kernel(const float* __re
       if (BN && bn.dres && q_ok) {            // the masked gradient is also the residual branch's gradient
 #pragma unroll
         for (int q = 0; q < 4; q++)
-          if (kFullB || lrow4 + q < B) ATW4(bn.dres, q) = gr[q];
+          if (kFullB || lrow4 + q < B) alignq_store::st16<alignq_store::kSiteBwdDres>(bn.dres, BO4(q), gr[q]);   // (BN: never LOOP)
       }
       float jt[PAIR ? 16 : 1];                 // dt/dx, on its way to Js
 #pragma unroll
@@ -1918,7 +1924,8 @@ __global__ __launch_bounds__(TFv * 8, 2) void site_bwd4_kernel(const float* __re
 #pragma unroll
               for (int e = 0; e < 4; e++) oo[e] += gj[PAIR ? 4 * q + e : 0];
             }
-            ATW4(dx, q) = make_float4(oo[0], oo[1], oo[2], oo[3]);
+            if constexpr (!LOOP) alignq_store::st16<alignq_store::kSiteBwdDx>(dx, BO4(q), make_float4(oo[0], oo[1], oo[2], oo[3]));
+            else ATW4(dx, q) = make_float4(oo[0], oo[1], oo[2], oo[3]);
             if (BN) {
 #pragma unroll
               for (int e = 0; e < 4; e++) {      // x is the conv output z here
