@@ -24,6 +24,11 @@ MAX_CORR_BATCH = _CONSTANTS["ALIGNQ_MAX_CORR_BATCH"]       # rows alignq_corr_fw
 ABI_VERSION = _CONSTANTS["ALIGNQ_ABI_VERSION"]
 EINVAL, EUNSUPPORTED = _CONSTANTS["ALIGNQ_EINVAL"], _CONSTANTS["ALIGNQ_EUNSUPPORTED"]
 
+# MOBILE_SIGNATURES: the entry points of include/alignq_mobile.h (MobileNet-V2's folded evaluation sites), a table of its own:
+# alignq.h's set of entry points and its ABI version are fixed, so an extension is declared next to it and never merged into SIGNATURES
+MOBILE_SIGNATURES, _MOBILE_STRUCTS, _MOBILE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_mobile.h"))
+CLAMP_NONE, CLAMP_RELU, CLAMP_RELU6 = (_MOBILE_CONSTANTS[n] for n in ("ALIGNQ_CLAMP_NONE", "ALIGNQ_CLAMP_RELU", "ALIGNQ_CLAMP_RELU6"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -33,6 +38,11 @@ class SiteBnArgs(ctypes.Structure):
 class SiteBwdBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bwd_bn_args (one site of alignq_site_bwd_apply_bn_twin; alignq_site_bwd_apply_bn's arguments)"""
     _fields_ = _STRUCTS["alignq_site_bwd_bn_args"]
+
+
+class EvalSite(ctypes.Structure):
+    """include/alignq_mobile.h: alignq_eval_site (one eval-mode batch-norm + quantiser + clamp)"""
+    _fields_ = _MOBILE_STRUCTS["alignq_eval_site"]
 
 
 _lib = None
@@ -53,6 +63,13 @@ def load():
         fn.restype, fn.argtypes = res, args
     if lib.alignq_abi_version() != ABI_VERSION:
         raise AlignQLibraryError("libalignq_hip.so ABI version mismatch; rebuild")
+    for name, (res, args) in MOBILE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_mobile.h): it was built before "
+                                     "csrc/mobile_eval_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
+        fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
 

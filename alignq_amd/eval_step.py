@@ -15,7 +15,9 @@ Differences from the reference's test(): an ADMM site comp
 leaves ADMM.D alone (test() discards the loss, and the D it stores is overwritten by the next training forward before anything
 reads it); ties are ranked as include/alignq.h states for alignq_eval_metrics.  This holds where alignq_bnq_eval_fwd applies
 (channels-last fp32, C a power of two in [4, 2048], a quantiser of 1..16 bits or none): any other site runs today's `model.eval()`
-composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D.
+composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D.  mobilenet.MobileNetV2 folds its sites
+itself inside the step (fused.site_eval_any / site_eval_twin / dw_site_eval, include/alignq_mobile.h: any C % 4 == 0 in [4, 2048],
+ReLU6, the stride-1 block tail, the depthwise convolution with its site as the epilogue).
 
     ev = EvalStep(skeleton, weights=export.PackedModel.load(path))     # evaluate from packed k-bit codes (export.py): begin()
                                                                        # unpacks them; the model's fp32 filters are never read"""
@@ -33,8 +35,8 @@ _FLAGS = ("fuse_bn", "fuse_relu", "use_qconv", "emit_bn_stats", "pack_bins", "_w
 
 
 class EvalStep(_CapturedStep):
-    """model: resnet.PreActResNet (tree "admm" or "cdf"), resnet_office.DANN (class logits at alpha = 0) or resnet_office.DSAN
-    (s_pred).  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
+    """model: resnet.PreActResNet (tree "admm" or "cdf"), resnet_office.DANN (class logits at alpha = 0), resnet_office.DSAN
+    (s_pred) or mobilenet.MobileNetV2.  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
     without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
     end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
 

@@ -1141,6 +1141,102 @@ def bn_site_res_relu_eval(bn, act, z, residual):
     return bn_eval_fwd(bn, z, k, config.args.act_range, L.FORMULA_ADMM, True, residual), 0.0
 
 
+# MobileNet-V2's evaluation sites (include/alignq_mobile.h, csrc/mobile_eval_kernels.hip): any channel count that is a multiple of
+# four, ReLU6 among the clamps, the stride-1 block's two-operand tail, and the site as the depthwise convolution's epilogue.  Each
+# returns None where its kernel does not apply; the caller then composes the modules.
+CLAMP_NONE, CLAMP_RELU, CLAMP_RELU6 = L.CLAMP_NONE, L.CLAMP_RELU, L.CLAMP_RELU6
+
+
+def _nhwc_f32(t) -> bool:
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0
+            and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def _eval_site(bn, act, C, z=None):
+    """(k, formula) of one folded site, or None: an eval-mode nn.BatchNorm2d with running statistics over C channels, C % 4 == 0 in
+    [4, 2048], a quantiser `_eval_k` has a width for, whose module states its formula; z (where given) CUDA fp32 channels-last."""
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and bn.running_mean is not None and bn.running_var is not None):
+        return None
+    if not (4 <= C <= 2048 and C % 4 == 0 and bn.num_features == C):
+        return None
+    if z is not None and not (_nhwc_f32(z) and z.shape[1] == C):
+        return None
+    k, formula = _eval_k(act), getattr(act, "_formula", None)
+    if k is None or formula not in (L.FORMULA_ADMM, L.FORMULA_CDF):
+        return None
+    return k, formula
+
+
+def _site_record(bn, z, k, clamp):
+    return L.EvalSite(L.ptr(z), L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var), float(bn.eps),
+                      int(k), int(clamp))
+
+
+def site_eval_any(bn, act, z, clamp, residual=None):
+    """clamp(act(bn.eval()(z)) [+ residual]) by one alignq_site_eval_fwd launch, or None."""
+    from . import config
+    kf = _eval_site(bn, act, z.shape[1] if torch.is_tensor(z) and z.dim() == 4 else 0, z)
+    if kf is None:
+        return None
+    if residual is not None:
+        if not (_nhwc_f32(residual) and residual.shape == z.shape):
+            return None
+    B, C, H, W = z.shape
+    y = torch.empty_like(z, memory_format=torch.channels_last)
+    site = _site_record(bn, z, kf[0], clamp)
+    rc = L.load().alignq_site_eval_fwd(ctypes.byref(site), B * H * W, C, float(config.args.act_range), int(kf[1]), L.ptr(residual),
+                                       L.ptr(y), L.stream_ptr())
+    L.check(rc, "alignq_site_eval_fwd")
+    return y
+
+
+def site_eval_twin(bnA, actA, zA, bnB, actB, zB, clampB):
+    """actA(bnA(zA)) + clampB(actB(bnB(zB))), the stride-1 inverted-residual block's tail, by one alignq_site_eval_twin_fwd launch;
+    None where either site has no folded form, the shapes differ or the two quantisers are on different formulas."""
+    from . import config
+    C = zA.shape[1] if torch.is_tensor(zA) and zA.dim() == 4 else 0
+    kfA, kfB = _eval_site(bnA, actA, C, zA), _eval_site(bnB, actB, C, zB)
+    if kfA is None or kfB is None or kfA[1] != kfB[1] or zA.shape != zB.shape:
+        return None
+    B, C, H, W = zA.shape
+    y = torch.empty_like(zA, memory_format=torch.channels_last)
+    a, b = _site_record(bnA, zA, kfA[0], CLAMP_NONE), _site_record(bnB, zB, kfB[0], clampB)
+    rc = L.load().alignq_site_eval_twin_fwd(ctypes.byref(a), ctypes.byref(b), B * H * W, C, float(config.args.act_range), int(kfA[1]),
+                                            L.ptr(y), L.stream_ptr())
+    L.check(rc, "alignq_site_eval_twin_fwd")
+    return y
+
+
+def dw_site_eval(conv, bn, act, x, clamp):
+    """clamp(act(bn.eval()(conv(x)))) for a depthwise 3x3 Conv2d_Q by one alignq_dwconv3x3_site_eval_fwd launch: the expanded tensor
+    between the convolution and its site is never written.  The filter is the one EvalStep parked in conv.quantize_fn._pre (the
+    weight itself at w_bit == 32).  None where the depthwise kernels do not apply, `use_qconv` is off or no filter is parked."""
+    from . import config, ops
+    if not (getattr(conv, "use_qconv", False) and hasattr(conv, "quantize_fn") and _nhwc_f32(x)):
+        return None
+    q = conv.quantize_fn
+    if getattr(q, "w_bit", 32) == 32:
+        wq = conv.weight
+    else:
+        pre = getattr(q, "_pre", None)
+        if pre is None or pre[0] is not conv.weight:
+            return None
+        wq = pre[1]
+    if not ops.qconv_dw_supported(x, wq, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, q.w_bit):
+        return None
+    B, C, H, W = x.shape
+    kf = _eval_site(bn, act, C)
+    if kf is None:
+        return None
+    s = int(conv.stride[0])
+    y = torch.empty((B, C, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    site = _site_record(bn, None, kf[0], clamp)
+    rc = L.load().alignq_dwconv3x3_site_eval_fwd(L.ptr(x), L.ptr(wq), ctypes.byref(site), B, H, W, C, s, float(config.args.act_range),
+                                                 int(kf[1]), L.ptr(y), L.stream_ptr())
+    L.check(rc, "alignq_dwconv3x3_site_eval_fwd")
+    return y
+
+
 def bn_only(bn, z, groups=1):
     """bn(z): the folded-family kernels when the tensor is channels-last fp32 in training mode, else the module itself
     (groups > 1: applied to the batch slices one after the other, as the reference's successive passes do)."""

@@ -12,6 +12,11 @@ Every weight and activation quantiser runs on this repository's kernels.  With u
 depthwise 3x3 convolutions (`layers[i].conv2`) run on csrc/dwconv_kernels.hip and the pointwise ones whose channel counts are
 multiples of 64 on the exact-product GEMMs; the other convolutions, batch-norm and the linear layer go to MIOpen / rocBLAS through
 PyTorch-ROCm.
+
+Inside eval_step.EvalStep (fused.eval_scope) both forwards fold every site into one launch (include/alignq_mobile.h): the eval-mode
+batch-norm, the quantiser and ReLU / ReLU6 (fused.site_eval_any), the depthwise convolution with its site as the epilogue
+(fused.dw_site_eval) and the stride-1 tail `act_q3(bn3(.)) + relu(act_skip(bn_s(.)))` (fused.site_eval_twin).  Outside it - training,
+or a bare `model.eval(); model(x)` - they are the composition above.
 """
 from __future__ import annotations
 
@@ -19,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import cdf_alignment as _cdf
+from . import fused
 
 
 class Block(nn.Module):
@@ -44,11 +50,37 @@ class Block(nn.Module):
                                           nn.BatchNorm2d(out_planes), self.act_skip, nn.ReLU(inplace=True))
 
     def forward(self, x):
+        if fused.eval_active():
+            return self._forward_eval(x)
         out = self.relu(self.act_q1(self.bn1(self.conv1(x))))
         out = self.relu(self.act_q2(self.bn2(self.conv2(out))))
         out = self.act_q3(self.bn3(self.conv3(out)))
         if self.stride == 1:
             out += self.shortcut(x)
+        return out
+
+    def _forward_eval(self, x):
+        """forward() inside fused.eval_scope (eval_step.EvalStep): every site one launch - batch-norm's running statistics, the
+        quantiser and ReLU6 folded (fused.site_eval_any), the depthwise convolution with its site as the epilogue
+        (fused.dw_site_eval), the stride-1 tail `act_q3(bn3(.)) + relu(act_skip(bn_s(.)))` in one pass (fused.site_eval_twin).  A site
+        whose kernel does not apply runs the composition of forward()."""
+        z = self.conv1(x)
+        out = fused.site_eval_any(self.bn1, self.act_q1, z, fused.CLAMP_RELU6)
+        if out is None:
+            out = self.relu(self.act_q1(self.bn1(z)))
+        mid = fused.dw_site_eval(self.conv2, self.bn2, self.act_q2, out, fused.CLAMP_RELU6)
+        if mid is None:
+            mid = self.relu(self.act_q2(self.bn2(self.conv2(out))))
+        z = self.conv3(mid)
+        if self.stride != 1:
+            out = fused.site_eval_any(self.bn3, self.act_q3, z, fused.CLAMP_NONE)
+            return self.act_q3(self.bn3(z)) if out is None else out
+        conv_s, bn_s, act_s, relu_s = self.shortcut
+        zs = conv_s(x)
+        out = fused.site_eval_twin(self.bn3, self.act_q3, z, bn_s, act_s, zs, fused.CLAMP_RELU)
+        if out is None:
+            out = self.act_q3(self.bn3(z))
+            out += relu_s(act_s(bn_s(zs)))
         return out
 
 
@@ -78,7 +110,17 @@ class MobileNetV2(nn.Module):
                 in_planes = out_planes
         return nn.Sequential(*layers)
 
+    def _site(self, bn, act, z):
+        """relu(act(bn(z))): one launch inside fused.eval_scope where the folded kernel applies, else the composition"""
+        out = fused.site_eval_any(bn, act, z, fused.CLAMP_RELU) if fused.eval_active() else None
+        return self.relu(act(bn(z))) if out is None else out
+
     def forward(self, x):
+        if fused.eval_active():
+            out = self.layers(self._site(self.bn1, self.act_q1, self.conv1(x)))
+            out = self._site(self.bn2, self.act_q2, self.conv2(out))
+            self.out = self.avg_pool2d(out)
+            return self.linear(self.out.view(self.out.size(0), -1))
         out = self.relu(self.act_q1(self.bn1(self.conv1(x))))
         out = self.layers(out)
         out = self.relu(self.act_q2(self.bn2(self.conv2(out))))

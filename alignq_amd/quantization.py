@@ -195,6 +195,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
             super().__init__()
             self.a_bit, self.stage = a_bit, stage
             self.uniform_q = uniform_quantize(k=a_bit)
+            self._formula = formula      # (read by the folded evaluation sites: fused.site_eval_any)
 
         def forward(self, x):
             return _plain_act(x, self.a_bit, self.stage)
