@@ -29,6 +29,11 @@ EINVAL, EUNSUPPORTED = _CONSTANTS["ALIGNQ_EINVAL"], _CONSTANTS["ALIGNQ_EUNSUPPOR
 MOBILE_SIGNATURES, _MOBILE_STRUCTS, _MOBILE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_mobile.h"))
 CLAMP_NONE, CLAMP_RELU, CLAMP_RELU6 = (_MOBILE_CONSTANTS[n] for n in ("ALIGNQ_CLAMP_NONE", "ALIGNQ_CLAMP_RELU", "ALIGNQ_CLAMP_RELU6"))
 
+# POINTWISE_SIGNATURES: the entry points of include/alignq_pointwise.h (the 1x1 Conv2d_Q convolutions at channel counts that are
+# multiples of 8), a third table for the same reason: neither of the two sets above moves
+POINTWISE_SIGNATURES, _POINTWISE_STRUCTS, _POINTWISE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_pointwise.h"))
+PW_FWD, PW_DGRAD, PW_WGRAD = (_POINTWISE_CONSTANTS[n] for n in ("ALIGNQ_PW_FWD", "ALIGNQ_PW_DGRAD", "ALIGNQ_PW_WGRAD"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -69,6 +74,13 @@ def load():
         except AttributeError:
             raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_mobile.h): it was built before "
                                      "csrc/mobile_eval_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
+        fn.restype, fn.argtypes = res, args
+    for name, (res, args) in POINTWISE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_pointwise.h): it was built before "
+                                     "csrc/pointwise_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib

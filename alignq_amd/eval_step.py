@@ -94,13 +94,18 @@ class EvalStep(_CapturedStep):
                     m.__dict__[f] = v
         self._saved = None
 
+    def _pack_filters(self):
+        """Whether begin() also leaves the filters' integer bins for the GEMM convolutions: the Office models, and any model whose
+        Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)) - once per evaluation, not per batch and layer"""
+        return self.qconv and (self._office or any(getattr(c, "use_qconv_pw", False) for c in self.all_convs))
+
     def _quantize_weights(self):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
         evaluation refreshes the SAME tensors in place: a captured graph keeps reading them."""
         convs = [c for c in self.all_convs if getattr(c.quantize_fn, "w_bit", 32) != 32 and hasattr(c.quantize_fn, "_pre")]
         if self._packed is not None:
             # from the packed codes (alignq_weight_unpack_multi) into tensors that persist: (weight, q, no cdf, no pdf, bins, image)
-            outs = self._packed.refresh(pack=self.qconv and self._office, images=self.filter_images)
+            outs = self._packed.refresh(pack=self._pack_filters(), images=self.filter_images)
             if self._wq is None or any(self._wq.get(id(c), (None, None))[1] is not outs[id(c)][0] for c in convs):
                 self._graph = None
             self._wq = {id(c): (c.weight, outs[id(c)][0], None, None, outs[id(c)][1], outs[id(c)][2]) for c in convs}
@@ -108,7 +113,7 @@ class EvalStep(_CapturedStep):
                 c.quantize_fn._pre = self._wq[id(c)]
                 c.quantize_fn._pre_keep = True
             return
-        fused.prequantize_weights(convs, pack=self.qconv and self._office, images=self.filter_images)
+        fused.prequantize_weights(convs, pack=self._pack_filters(), images=self.filter_images)
         fresh = {id(c): c.quantize_fn._pre for c in convs}
         if self._wq is not None and set(self._wq) == set(fresh):
             for key, old in self._wq.items():

@@ -10,8 +10,9 @@ Linear(1280, num_classes).
 
 Every weight and activation quantiser runs on this repository's kernels.  With use_hip_convs(model) and channels-last inputs the
 depthwise 3x3 convolutions (`layers[i].conv2`) run on csrc/dwconv_kernels.hip and the pointwise ones whose channel counts are
-multiples of 64 on the exact-product GEMMs; the other convolutions, batch-norm and the linear layer go to MIOpen / rocBLAS through
-PyTorch-ROCm.
+multiples of 64 on the exact-product GEMMs; with use_hip_convs(model, pointwise=True) the other pointwise ones (channel counts
+multiples of 8) run on csrc/pointwise_kernels.hip with the same arithmetic; the stem (and, without the opt-in, those pointwise
+convolutions), batch-norm and the linear layer go to MIOpen / rocBLAS through PyTorch-ROCm.
 
 Inside eval_step.EvalStep (fused.eval_scope) both forwards fold every site into one launch (include/alignq_mobile.h): the eval-mode
 batch-norm, the quantiser and ReLU / ReLU6 (fused.site_eval_any), the depthwise convolution with its site as the epilogue
@@ -132,12 +133,17 @@ def mobile_v2(wbit, abit, stage, num_classes=10):
     return MobileNetV2(Block, wbit, abit, stage, num_classes=num_classes)
 
 
-def use_hip_convs(model):
+def use_hip_convs(model, pointwise=False):
     """Channels-last parameters plus `use_qconv` on every Conv2d_Q (what TrainStep(channels_last=True, qconv=True) does for its
     models): with channels-last inputs the convolutions this repository has kernels for then run on them.  Values, parameter
-    names and state_dict are unchanged."""
+    names and state_dict are unchanged.
+    pointwise=True also sets `use_qconv_pw`: the 1x1 convolutions whose channel counts are multiples of 8 (and not both of 64) run
+    on alignq_pwconv_* (include/alignq_pointwise.h) instead of F.conv2d - every supported shape, whatever its speed: the point is
+    the defined arithmetic.  Off by default: every launch is then what it was."""
     model = model.to(memory_format=torch.channels_last)
     for m in model.modules():
         if hasattr(m, "quantize_fn"):
             m.use_qconv = True
+            if pointwise:
+                m.use_qconv_pw = True
     return model

@@ -318,6 +318,10 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                                                      ops.level_count(input), 1, False, bins)
                     if ops.qconv_dw_supported(*args):        # MobileNet-V2's depthwise 3x3 (csrc/dwconv_kernels.hip)
                         return ops.QConvDwFn.apply(input, weight_q, self.stride[0])
+                    # opt-in on top of use_qconv (mobilenet.use_hip_convs(model, pointwise=True)): the 1x1 convolutions whose channel
+                    # counts are multiples of 8 (csrc/pointwise_kernels.hip); the multiples of 64 stay on the branch above
+                    if getattr(self, "use_qconv_pw", False) and ops.qconv_pw_supported(*args):
+                        return ops.QConvPwFn.apply(input, weight_q, self.quantize_fn.w_bit, self.quantize_fn.take_bins(weight_q))
                 return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
             def forward_with_shortcut(self, input):

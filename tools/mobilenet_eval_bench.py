@@ -5,16 +5,19 @@ Prints one JSON line; --out also writes it to a file.
 
     python tools/mobilenet_eval_bench.py [--batches 100] [--rounds 5] [--out profiles/mobilenet_eval_bench.json]
 
-Whole evaluation, three paths timed in interleaved rounds in one process (median, best and the spread of the rounds reported):
+Whole evaluation, four paths timed in interleaved rounds in one process (median, best and the spread of the rounds reported):
   model_eval          the reference's test() on this repository's modules: eval mode, no_grad, channels-last, use_qconv,
                       F.cross_entropy + topk accuracy with their host reads per batch;
   eval_step_composed  captured EvalStep with every site the `model.eval()` composition - mobilenet.py's folded route switched off,
                       which is EvalStep(mobile_v2(...)) as it stood before the folded sites existed: the baseline;
   eval_step_folded    captured EvalStep with the folded sites (alignq_site_eval_fwd, alignq_site_eval_twin_fwd,
-                      alignq_dwconv3x3_site_eval_fwd).
+                      alignq_dwconv3x3_site_eval_fwd);
+  eval_step_pointwise the same on a copy of the model with mobilenet.use_hip_convs(model, pointwise=True): the 1x1 convolutions whose
+                      channel counts are no multiples of 64 on alignq_pwconv_fwd instead of MIOpen, their bins packed once in begin().
 Per depthwise shape (C, H_in, stride) of the network at batch 100: a graph of REPS fused launches against a graph of REPS
 (alignq_dwconv3x3_nhwc_fwd, alignq_site_eval_fwd) pairs, replayed alternately; microseconds per site."""
 import argparse
+import copy
 import ctypes
 import json
 import os
@@ -102,9 +105,11 @@ def whole_evaluation(dev, batches, rounds):
     xs = [torch.randn(BATCH, 3, 32, 32, device=dev).contiguous(memory_format=torch.channels_last) for _ in range(4)]
     ys = [torch.randint(0, 10, (BATCH,), device=dev) for _ in range(4)]
     ev_c, ev_f = EvalStep(net), EvalStep(net)
+    ev_p = EvalStep(M.use_hip_convs(copy.deepcopy(net), pointwise=True))
     paths = {"model_eval": lambda: run_model_eval(net, xs, ys, batches),
              "eval_step_composed": lambda: run_eval_step(ev_c, xs, ys, batches, True),
-             "eval_step_folded": lambda: run_eval_step(ev_f, xs, ys, batches, False)}
+             "eval_step_folded": lambda: run_eval_step(ev_f, xs, ys, batches, False),
+             "eval_step_pointwise": lambda: run_eval_step(ev_p, xs, ys, batches, False)}
     for f in paths.values():          # warm-up round (plans, allocator pools, the captures), not timed
         f()
     times, results = {k: [] for k in paths}, {}
@@ -121,6 +126,7 @@ def whole_evaluation(dev, batches, rounds):
                "rounds_ms_per_batch": [1e3 * t / batches for t in v]} for k, v in times.items()}
     rec["folded_over_composed"] = rec["eval_step_folded"]["images_per_s"] / rec["eval_step_composed"]["images_per_s"]
     rec["folded_over_model_eval"] = rec["eval_step_folded"]["images_per_s"] / rec["model_eval"]["images_per_s"]
+    rec["pointwise_over_folded"] = rec["eval_step_pointwise"]["images_per_s"] / rec["eval_step_folded"]["images_per_s"]
     rec["prec1"] = {k: float(v[1]) for k, v in results.items()}
     rec["batch"], rec["bits"], rec["batches"] = BATCH, BITS, batches
     return rec
