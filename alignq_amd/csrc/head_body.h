@@ -11,8 +11,16 @@ namespace alignq_head {
 
 constexpr int kMaxC = 256, kMaxK = 64;
 
+// dl[b][j] = g * (probs[b][j] - [j == target_b]) / B   (mean reduction of the loss over all B rows; gs = g / B, g = upstream scalar).
+// A row whose target lies outside [0, K) has the constant loss 0 in head_fwd_body, so its dl is exactly 0 for every class: it adds
+// nothing to dW / dbias and its dfeat rows are zero (the rule alignq_eval_metrics and alignq_lmmd_fwd state for their labels).
+__device__ __forceinline__ float head_dl(float gs, const float* __restrict__ probs, const int64_t* __restrict__ target, int b,
+                                         int j, int K) {
+  const int64_t y = target[b];
+  return (y >= 0 && y < K) ? gs * (probs[(int64_t)b * K + j] - (y == j ? 1.f : 0.f)) : 0.f;
+}
+
 // blocks [0, B): dfeat[b][p][c] = (1/HW) sum_j dl[b][j] W[j][c] for every pixel p;  blocks [B, B+K): dW[j][:], dbias[j]
-// with dl[b][j] = g * (probs[b][j] - [j == target_b]) / B   (mean reduction of the loss; g = upstream scalar)
 // `block`: index among the B + K workgroups of this role (256 threads each)
 __device__ __forceinline__ void head_bwd_body(const float* __restrict__ g, const float* __restrict__ probs,
                                               const int64_t* __restrict__ target, const float* __restrict__ pooled,
@@ -28,7 +36,7 @@ __device__ __forceinline__ void head_bwd_body(const float* __restrict__ g, const
   const int c = tid % C, part = tid / C;
   if (block < B) {
     const int b = block;
-    if (tid < K) sd[tid] = gs * (probs[(int64_t)b * K + tid] - (target[b] == tid ? 1.f : 0.f));
+    if (tid < K) sd[tid] = head_dl(gs, probs, target, b, tid, K);
     __syncthreads();
     if (part < parts) {
       float s = 0.f;
@@ -44,7 +52,7 @@ __device__ __forceinline__ void head_bwd_body(const float* __restrict__ g, const
     // dl[b] for this class (B <= 1024 staged in LDS; larger batches fall back to recomputing in the loop)
     const bool staged = B <= 1024;
     if (staged)
-      for (int b = tid; b < B; b += 256) sdl[b] = gs * (probs[(int64_t)b * K + j] - (target[b] == j ? 1.f : 0.f));
+      for (int b = tid; b < B; b += 256) sdl[b] = head_dl(gs, probs, target, b, j, K);
     __syncthreads();
     float dw = 0.f;
     if (part < parts) {
@@ -57,12 +65,12 @@ __device__ __forceinline__ void head_bwd_body(const float* __restrict__ g, const
         for (int u = 0; u < 8; u++) v[u] = pooled[(int64_t)(b + u) * C + c];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-          const float d = staged ? sdl[b + u] : gs * (probs[(int64_t)(b + u) * K + j] - (target[b + u] == j ? 1.f : 0.f));
+          const float d = staged ? sdl[b + u] : head_dl(gs, probs, target, b + u, j, K);
           dw = __fmaf_rn(d, v[u], dw);
         }
       }
       for (; b < b1; b++) {
-        const float d = staged ? sdl[b] : gs * (probs[(int64_t)b * K + j] - (target[b] == j ? 1.f : 0.f));
+        const float d = staged ? sdl[b] : head_dl(gs, probs, target, b, j, K);
         dw = __fmaf_rn(d, pooled[(int64_t)b * C + c], dw);
       }
     }
@@ -75,7 +83,7 @@ __device__ __forceinline__ void head_bwd_body(const float* __restrict__ g, const
     }
     if (tid == 0 && dbias) {
       float db = 0.f;
-      for (int b = 0; b < B; b++) db += staged ? sdl[b] : gs * (probs[(int64_t)b * K + j] - (target[b] == j ? 1.f : 0.f));
+      for (int b = 0; b < B; b++) db += staged ? sdl[b] : head_dl(gs, probs, target, b, j, K);
       dbias[j] = db;
     }
   }

@@ -539,7 +539,9 @@ int alignq_bn_bwd_totals(const float* dx_part, int B, int C, int HW, float* ktot
 /* ---- classifier head of the training harness fused with its loss (channels-last features feat [B,HW,C]):
  * pooled = mean over HW; logits = pooled W^T + bias (W [K,C]); loss[b] = cross-entropy(logits[b], target[b]) per sample (the
  * caller averages); probs = softmax(logits) kept for the backward.  Backward for the MEAN of loss with upstream scalar *g:
- * dfeat, dW, dbias (dbias may be NULL).  C <= 256, K <= 64.  Reference: model/resnet.py:127-129 + main.py's criterion.   */
+ * dfeat, dW, dbias (dbias may be NULL).  C <= 256, K <= 64.  Reference: model/resnet.py:127-129 + main.py's criterion.
+ * A row whose target lies outside [0, K) has loss[b] = 0 (it still counts in the mean's divisor B) and no gradient: its
+ * dfeat rows are exactly zero and it adds nothing to dW / dbias.                                                          */
 /* ce_mean (or NULL): additionally *ce_mean = mean_b loss[b], formed in index order by the workgroup that finishes last
  * (`counter`: one zero-initialised unsigned the kernel re-arms); site_scal / n_sites / trans_total (or NULL / 0 / NULL, need
  * ce_mean): *trans_total = sum_i site_scal[4 i], the total of the sites' transition losses (the `scal` rows of

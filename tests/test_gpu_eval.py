@@ -9,6 +9,7 @@ NumPy as in the oracle (checked against the oracle's own residual / ReLU argumen
 import itertools
 import os
 import sys
+import warnings
 
 import numpy as np
 import pytest
@@ -161,17 +162,26 @@ def run_metrics(dev, batches, K):
     return acc.cpu().numpy()
 
 
-@pytest.mark.parametrize("K", [10, 31, 1000])
+@pytest.mark.parametrize("K", [10, 31, 1000,
+                               1, 4, 5,                        # below 5 classes every valid finite row is a top-5 hit
+                               64, 65, 1024])                  # one pass of the 64 lanes, one class more, the largest K
 def test_eval_metrics_against_numpy(dev, K):
     rng = np.random.default_rng(K)
     batches = []
-    for B in (100, 28, 7):
+    for B in (100, 28, 7,
+              1, 2, 4, 5):                                     # the four-row groups' remainders: 1, 2, 0, 1 rows in the last group
         lg = (rng.standard_normal((B, K)) * 3).astype(np.float32)
         tg = rng.integers(0, K, B).astype(np.int64)
         lg[np.arange(0, B, 3), tg[::3]] += 4.0                 # a good share of correct rows
-        lg[1, (tg[1] + 1) % K] = lg[1, tg[1]]                  # a tie with the target: does not count against it
-        tg[2], tg[3] = -1, K                                   # out of range on both sides
+        if B > 1:
+            lg[1, (tg[1] + 1) % K] = lg[1, tg[1]]              # a tie with the target: does not count against it
+        if B > 3:
+            tg[2], tg[3] = -1, K                               # out of range on both sides
         batches.append((lg, tg))
+    if K < 5:
+        for lg, tg in batches:
+            e = metrics_numpy(lg, tg)
+            assert e[2] == int(((tg >= 0) & (tg < K)).sum())   # (every valid row is a top-5 hit)
     raw = run_metrics(dev, batches, K)
     exp = [metrics_numpy(lg, tg) for lg, tg in batches]
     ce = float(raw[:1].view(np.float64)[0])
@@ -186,7 +196,9 @@ def test_eval_metrics_against_numpy(dev, K):
     lg[5, 0] = np.nan
     lg[6, tg[6]] = np.nan
     raw_n = run_metrics(dev, [(lg, tg)], K)
-    e = metrics_numpy(lg, tg)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)        # K = 1: the NaN is the whole row (np.nanmax warns)
+        e = metrics_numpy(lg, tg)
     assert raw_n[1:].tolist() == [e[1], e[2], e[3]]
     assert np.isnan(raw_n[:1].view(np.float64)[0])
 
