@@ -14,6 +14,8 @@ from typing import Callable, List, Sequence
 import torch
 import torch.distributed as dist
 
+from . import paths
+
 
 class FlatBucket:
     """A persistent flat buffer with views: tensors are packed / unpacked with one fused copy each way."""
@@ -146,11 +148,8 @@ def attach(train_step, group=None, force=False, global_corr=False):
     if global_corr:
         # scoped to THIS model's quantiser modules (not the process-global config): other models / steps in the process keep
         # the per-rank semantics; detach() restores what is changed here
-        undo = {"fuse_bn": [], "sites": [], "deferred": train_step._deferred}
+        undo = {"fuse_bn": paths.apply(train_step.model, fuse_bn=False), "sites": [], "deferred": train_step._deferred}
         for m in train_step.model.modules():
-            if hasattr(m, "fuse_bn"):
-                undo["fuse_bn"].append((m, m.fuse_bn))
-                m.fuse_bn = False
             if hasattr(m, "a_bit") and hasattr(m, "opt"):
                 undo["sites"].append(m)
                 m.global_corr = True if group is None else group
@@ -169,8 +168,7 @@ def detach(train_step):
     train_step.grad_hook = None
     undo = getattr(train_step, "_global_corr_undo", None)
     if undo is not None:
-        for m, v in undo["fuse_bn"]:
-            m.fuse_bn = v
+        paths.restore(undo["fuse_bn"])
         for m in undo["sites"]:
             m.global_corr = None
             # the exact-global sites stored D WITH its autograd graph (ADMM.forward, utils/admm.py:25): dropped here, or the last

@@ -27,11 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import fused
+from . import fused, paths
 from .train_step import _CapturedStep
-
-_MISSING = object()
-_FLAGS = ("fuse_bn", "fuse_relu", "use_qconv", "emit_bn_stats", "pack_bins", "_wq_stage")
 
 
 class EvalStep(_CapturedStep):
@@ -66,38 +63,10 @@ class EvalStep(_CapturedStep):
         self._init_capture(None)
 
     # ------------------------------------------------------------------------------------------- lifecycle
-    def _set_flags(self):
-        m_all = list(self.model.modules())
-        self._saved = [(m, m.training, {f: m.__dict__.get(f, _MISSING) for f in _FLAGS}) for m in m_all]
-        for m in m_all:
-            if m.__dict__.get("_wq_stage") is not None:
-                m._wq_stage = None               # (OfficeTrainStep.stage_weights re-quantises per stage and batch)
-            if hasattr(m, "quantize_fn"):
-                m.use_qconv = self.qconv
-                m.emit_bn_stats = False          # no batch statistics in evaluation
-            if hasattr(m, "fuse_bn") or hasattr(m, "act_q0") or (hasattr(m, "act_q1") and hasattr(m, "act_q3")):
-                m.fuse_bn = self.channels_last
-                if self._office:
-                    m.fuse_relu = True
-            if self._office and hasattr(m, "act_q1") and hasattr(m, "act_q2") and hasattr(m, "act_q3"):
-                m.pack_bins = self.pack_bins
-            elif hasattr(m, "conv1") and hasattr(m, "act_q0") and hasattr(m, "bn0"):
-                m.pack_bins = self.pack_bins
-
-    def _restore_flags(self):
-        for m, training, flags in self._saved or ():
-            m.training = training
-            for f, v in flags.items():
-                if v is _MISSING:
-                    m.__dict__.pop(f, None)
-                else:
-                    m.__dict__[f] = v
-        self._saved = None
-
     def _pack_filters(self):
         """Whether begin() also leaves the filters' integer bins for the GEMM convolutions: the Office models, and any model whose
         Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)) - once per evaluation, not per batch and layer"""
-        return self.qconv and (self._office or any(getattr(c, "use_qconv_pw", False) for c in self.all_convs))
+        return self.qconv and (self._office or any(c.use_qconv_pw for c in self.all_convs))
 
     def _quantize_weights(self):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
@@ -129,7 +98,10 @@ class EvalStep(_CapturedStep):
     def begin(self):
         if self._saved is not None:
             raise RuntimeError("EvalStep.begin: already begun (call end() first)")
-        self._set_flags()
+        # (emit_bn_stats: no batch statistics in evaluation; _wq_stage: OfficeTrainStep.stage_weights re-quantises per stage and batch)
+        flags = paths.apply(self.model, use_qconv=self.qconv, emit_bn_stats=False, fuse_bn=self.channels_last, fuse_relu=True,
+                            pack_bins=self.pack_bins, _wq_stage=None)
+        self._saved = (flags, [(m, m.training) for m in self.model.modules()])
         try:
             self.model.eval()
             dev = next(self.model.parameters()).device
@@ -150,7 +122,11 @@ class EvalStep(_CapturedStep):
             q = c.quantize_fn
             if hasattr(q, "_pre"):
                 q._pre, q._pre_keep = None, False
-        self._restore_flags()
+        flags, modes = self._saved or ((), ())
+        paths.restore(flags)
+        for m, training in modes:
+            m.training = training
+        self._saved = None
         return self
 
     __enter__ = begin

@@ -255,7 +255,7 @@ class PackedFilters:
                 bins = image = None
                 if pack and 1 <= k <= 8 and q.numel() % 4 == 0:
                     bins = (torch.empty_like(q, dtype=torch.int16), torch.empty_like(q, dtype=torch.int16))
-                if images and 1 <= k <= 8 and getattr(c, "use_qconv", False):
+                if images and 1 <= k <= 8 and c.use_qconv:
                     geo = fused.filter_image_geometry(c.weight)
                     if geo is not None:
                         image = (torch.empty(lib.alignq_filter_image_bytes(*geo[:3]), dtype=torch.uint8, device=dev), geo)

@@ -112,7 +112,7 @@ def prequantize_weights(convs, pack=False, images=False):
             lib = L.load()
             imgs = []
             for c in cs:
-                geo = filter_image_geometry(c.weight) if getattr(c, "use_qconv", False) else None
+                geo = filter_image_geometry(c.weight) if c.use_qconv else None
                 imgs.append(None if geo is None else
                             torch.empty(lib.alignq_filter_image_bytes(*geo[:3]), dtype=torch.uint8, device=c.weight.device))
             if all(im is None for im in imgs):
@@ -1212,7 +1212,7 @@ def dw_site_eval(conv, bn, act, x, clamp):
     between the convolution and its site is never written.  The filter is the one EvalStep parked in conv.quantize_fn._pre (the
     weight itself at w_bit == 32).  None where the depthwise kernels do not apply, `use_qconv` is off or no filter is parked."""
     from . import config, ops
-    if not (getattr(conv, "use_qconv", False) and hasattr(conv, "quantize_fn") and _nhwc_f32(x)):
+    if not (conv.use_qconv and _nhwc_f32(x)):
         return None
     q = conv.quantize_fn
     if getattr(q, "w_bit", 32) == 32:

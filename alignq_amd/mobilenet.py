@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import cdf_alignment as _cdf
-from . import fused
+from . import fused, paths
 
 
 class Block(nn.Module):
@@ -141,9 +141,5 @@ def use_hip_convs(model, pointwise=False):
     on alignq_pwconv_* (include/alignq_pointwise.h) instead of F.conv2d - every supported shape, whatever its speed: the point is
     the defined arithmetic.  Off by default: every launch is then what it was."""
     model = model.to(memory_format=torch.channels_last)
-    for m in model.modules():
-        if hasattr(m, "quantize_fn"):
-            m.use_qconv = True
-            if pointwise:
-                m.use_qconv_pw = True
+    paths.apply(model, use_qconv=True, **({"use_qconv_pw": True} if pointwise else {}))
     return model

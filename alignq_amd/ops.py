@@ -874,7 +874,7 @@ class QTransitionFn(torch.autograd.Function):
 
 def transition_supported(conv3, conv1, x, w3, w1) -> bool:
     """Both convolutions of a transition block on this repository's kernels, gradients needed for x and both filters."""
-    if not (getattr(conv3, "use_qconv", False) and getattr(conv1, "use_qconv", False)):
+    if not (conv3.use_qconv and conv1.use_qconv):
         return False
     if conv3.quantize_fn.w_bit != conv1.quantize_fn.w_bit or not (x.requires_grad and w3.requires_grad and w1.requires_grad):
         return False

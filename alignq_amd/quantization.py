@@ -118,7 +118,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
         """relu(_plain_act(x)); one launch each way when the quantiser is active."""
         if (a_bit == 32) or not (x.is_cuda and x.dtype == torch.float32 and x.numel() % 4 == 0):
             return torch.relu(_plain_act(x, a_bit, stage))
-        if getattr(config.args, "pack_bins", False) and ops.bin_dtype(a_bit, config.args.act_range, formula) is not None:
+        if config.args.pack_bins and ops.bin_dtype(a_bit, config.args.act_range, formula) is not None:
             # N2: the node keeps the 1-2 B level index instead of fp32 relu(x_q) (no narrow form: 16 < k < 32 or a large
             # act_range -> the fp32 path below, like the reference)
             return ops.ActQuantPackedFn.apply(x, a_bit, config.args.act_range, formula, True)[0]
@@ -257,6 +257,11 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
 
     def conv2d_Q_fn(w_bit, stage):
         class Conv2d_Q(nn.Conv2d):
+            # kernel-path flags, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+            use_qconv = False
+            use_qconv_pw = False
+            emit_bn_stats = False
+
             def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                          bias=True):
                 super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias)
@@ -271,17 +276,17 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     # N2: the input is a packed handle (fused.bn_site(pack=True)): its values are int8 / int16 level
                     # indices; the 3x3 body convolution reads them directly, anything else gets the dequantised tensor
                     bins, a_bit = packed
-                    if (getattr(self, "use_qconv", False) and weight_q.is_cuda
+                    if (self.use_qconv and weight_q.is_cuda
                             and ops.qconv3x3_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
                                                              self.groups, self.bias, self.quantize_fn.w_bit)):
                         return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit,
                                                                self.quantize_fn.take_image(weight_q))
-                    if (getattr(self, "use_qconv", False) and bins.dtype == torch.int16 and ops.level_count(input)
+                    if (self.use_qconv and bins.dtype == torch.int16 and ops.level_count(input)
                             and ops.qconv_gemm_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
                                                                self.groups, self.bias, self.quantize_fn.w_bit)):
                         # the ResNet-50 shapes: the GEMM kernels read the int16 indices directly (forward and filter gradient)
                         fb = self.quantize_fn.take_bins(weight_q)
-                        if getattr(self, "emit_bn_stats", False):
+                        if self.emit_bn_stats:
                             from . import fused
                             return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
                                                                     ops.level_count(input), fused.conv_groups(), fb, bins)
@@ -289,9 +294,9 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                                                      1, False, fb, bins)
                     from . import fused
                     input = fused.materialize(input)
-                # opt-in (TrainStep(channels_last=True) sets use_qconv): the convolutions on the matrix cores
+                # opt-in: the convolutions on the matrix cores
                 # (with the batch-norm statistics of the output as a by-product for fused.bn_site)
-                if getattr(self, "use_qconv", False):
+                if self.use_qconv:
                     args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):
@@ -304,13 +309,13 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                         return ops.QConvStemFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit)
                     if ops.qconv_stem7_supported(*args):     # the Office stem (7x7, stride 2, 3 -> 64 channels)
                         bins = self.quantize_fn.take_bins(weight_q)
-                        if getattr(self, "emit_bn_stats", False):
+                        if self.emit_bn_stats:
                             from . import fused
                             return ops.QConvStem7Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, fused.conv_groups(), bins)
                         return ops.QConvStem7Fn.apply(input, weight_q, self.quantize_fn.w_bit, 1, False, bins)
                     if ops.qconv_gemm_supported(*args):      # the ResNet-50 shapes: exact-product GEMMs (csrc/qgemm_kernels.hip)
                         bins = self.quantize_fn.take_bins(weight_q)
-                        if getattr(self, "emit_bn_stats", False):     # the batch-norm behind this convolution takes its statistics
+                        if self.emit_bn_stats:     # the batch-norm behind this convolution takes its statistics
                             from . import fused                        # from the epilogue (fused.conv_partials)
                             return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
                                                                     ops.level_count(input), fused.conv_groups(), bins)
@@ -320,7 +325,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                         return ops.QConvDwFn.apply(input, weight_q, self.stride[0])
                     # opt-in on top of use_qconv (mobilenet.use_hip_convs(model, pointwise=True)): the 1x1 convolutions whose channel
                     # counts are multiples of 8 (csrc/pointwise_kernels.hip); the multiples of 64 stay on the branch above
-                    if getattr(self, "use_qconv_pw", False) and ops.qconv_pw_supported(*args):
+                    if self.use_qconv_pw and ops.qconv_pw_supported(*args):
                         return ops.QConvPwFn.apply(input, weight_q, self.quantize_fn.w_bit, self.quantize_fn.take_bins(weight_q))
                 return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
@@ -330,7 +335,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 kernels (and a gradient is needed) the alias is an output of the same autograd node, so the second gradient
                 is added inside the data-gradient kernel; otherwise plainly (forward(input), input)."""
                 weight_q = self.quantize_fn(self.weight)
-                if getattr(self, "use_qconv", False) and input.requires_grad:
+                if self.use_qconv and input.requires_grad:
                     args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):

@@ -26,6 +26,10 @@ def conv1x1(wbit, stage, cin, cout, stride=1):
 
 class Bottleneck(nn.Module):
     expansion = 4
+    # kernel-path flags, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+    fuse_bn = False
+    fuse_relu = False
+    pack_bins = False
 
     def __init__(self, wbit, abit, stage, inplanes, planes, stride=1, downsample=None, base_width=64):
         super().__init__()
@@ -58,7 +62,7 @@ class Bottleneck(nn.Module):
             from . import fused
             x, x_short = fused.fork_block_input(x)
             identity = x_short
-            pack = getattr(self, "pack_bins", False)        # N2: conv2 / conv3 read int16 level indices instead of fp32 values
+            pack = self.pack_bins        # N2: conv2 / conv3 read int16 level indices instead of fp32 values
             out = self.act_q1.forward_bn_relu(self.bn1, self.conv1(x), groups, pack)
             out = self.act_q2.forward_bn_relu(self.bn2, self.conv2(out), groups, pack)
             if self.downsample is not None:
@@ -66,26 +70,26 @@ class Bottleneck(nn.Module):
             out, loss = self.act_q3.forward_bn_res_relu(self.bn3, self.conv3(out), identity, groups, loss_vec=loss_vec)
             return out, loss              # (= 0. + loss without the launch that forms it)
         x_short = x
-        if getattr(self, "fuse_bn", False):         # opt-in (OfficeTrainStep): batch-norm + quantiser + ReLU as one chain
+        if self.fuse_bn:         # opt-in (OfficeTrainStep): batch-norm + quantiser + ReLU as one chain
             from . import fused
             x, x_short = fused.fork_block_input(x)
             identity = x_short
-            pack = getattr(self, "pack_bins", False)
+            pack = self.pack_bins
             out = self.act_q1.forward_bn_relu(self.bn1, self.conv1(x), 1, pack)
             out = self.act_q2.forward_bn_relu(self.bn2, self.conv2(out), 1, pack)
-        elif getattr(self, "fuse_relu", False):     # opt-in: quantiser + ReLU in one launch each way
+        elif self.fuse_relu:     # opt-in: quantiser + ReLU in one launch each way
             out = self.act_q1.forward_relu(self.bn1(self.conv1(x)))
             out = self.act_q2.forward_relu(self.bn2(self.conv2(out)))
         else:
             out = self.relu(self.act_q1(self.bn1(self.conv1(x))))
             out = self.relu(self.act_q2(self.bn2(self.conv2(out))))
-        if getattr(self, "fuse_bn", False):         # bn3 folded into the site kernels, the downsample batch-norm on the same family
+        if self.fuse_bn:         # bn3 folded into the site kernels, the downsample batch-norm on the same family
             if self.downsample is not None:
                 from . import fused
                 identity = fused.bn_only(self.downsample[1], self.downsample[0](x_short))
             out, loss = self.act_q3.forward_bn_res_relu(self.bn3, self.conv3(out), identity)
             return out, loss              # (= 0. + loss without the launch that forms it)
-        if getattr(self, "fuse_relu", False):       # `out += identity; relu` inside the site kernels
+        if self.fuse_relu:       # `out += identity; relu` inside the site kernels
             z = self.bn3(self.conv3(out))
             if self.downsample is not None:
                 identity = self.downsample(x)
@@ -101,6 +105,10 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
+    fuse_bn = False                # kernel-path flags (alignq_amd.paths)
+    fuse_relu = False
+    _wq_stage = None               # hook: OfficeTrainStep.stage_weights' per-stage weight quantiser
+
     def __init__(self, wbit, abit, stage, block, layers, num_classes=1000, width_per_group=64):
         super().__init__()
         self.wbit, self.abit, self.stage = wbit, abit, stage
@@ -144,7 +152,7 @@ class ResNet(nn.Module):
         trans_loss = 0.
         from . import fused
         # staged weight quantisation (OfficeTrainStep.stage_weights, data parallelism): stage i's filters right before stage i
-        wq = getattr(self, "_wq_stage", None) or (lambda i: None)
+        wq = self._wq_stage or (lambda i: None)
         wq(0)
         if groups > 1:
             q0 = self.act_q0.forward_bn_relu(self.bn1, self.conv1(x), groups)
@@ -168,12 +176,12 @@ class ResNet(nn.Module):
             # (the folded sites return the VECTOR of their slices' losses - a view, no kernel: one concatenation + one sum)
             total = total_t + rest if tens else rest
             return torch.flatten(self.avgpool(x), 1), total
-        if getattr(self, "fuse_bn", False):
+        if self.fuse_bn:
             q0 = self.act_q0.forward_bn_relu(self.bn1, self.conv1(x))
             x = self.maxpool(q0)
             if hasattr(q0, "_alignq_levels"):
                 x._alignq_levels = q0._alignq_levels
-        elif getattr(self, "fuse_relu", False):
+        elif self.fuse_relu:
             x = self.maxpool(self.act_q0.forward_relu(self.bn1(self.conv1(x))))
         else:
             x = self.maxpool(self.relu(self.act_q0(self.bn1(self.conv1(x)))))

@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import config
+from . import config, paths
 from .fused import DeferredLosses, DeferredWgrads, HeadCEFn, head_ce_supported, prequantize_weights
 from .optimizer import ADMM_OPT, SGD, sgd_admm_step
 from .schedule import HyperBlock, Schedule, office_rate, ramp
@@ -382,25 +382,21 @@ class TrainStep(_CapturedStep):
         BN fold has a channels-last form."""
         if channels_last:
             model = model.to(memory_format=torch.channels_last)
-            if qconv:    # Conv2d_Q's 3x3 body convolutions (forward + data gradient) on the matrix cores, exact products
-                for m in model.modules():
-                    if hasattr(m, "quantize_fn"):
-                        m.use_qconv = True
-        if channels_last and qconv and fuse_bn and pack_bins:
+        self.channels_last = channels_last
+        self.qconv = bool(channels_last and qconv)
+        paths.apply(
+            model,
+            # Conv2d_Q's 3x3 body convolutions (forward + data gradient) on the matrix cores, exact products
+            use_qconv=self.qconv,
+            # fold BN into the site kernels where shapes allow (training, 64 < batch <= 128); no-op otherwise
+            fuse_bn=bool(fuse_bn),
             # N2 (SURVEY 8f): relu(act_q0(bn0(.))) of every block feeds conv1 only -> it is stored as its int8 / int16 level
             # index (no fp32 copy): the site forward writes, the convolution forward / filter gradient and the site backward's
             # ReLU mask read 1-2 B per element instead of 4
-            for m in model.modules():
-                if hasattr(m, "conv1") and hasattr(m, "act_q0") and hasattr(m, "bn0"):
-                    m.pack_bins = True
-        self.channels_last = channels_last
-        self.filter_images = bool(filter_images and channels_last and qconv and torch.cuda.is_available())
-        self._wgrads = DeferredWgrads(fresh_grads=True) if (channels_last and qconv and torch.cuda.is_available()) else None
+            pack_bins=bool(self.qconv and fuse_bn and pack_bins))
+        self.filter_images = bool(filter_images and self.qconv and torch.cuda.is_available())
+        self._wgrads = DeferredWgrads(fresh_grads=True) if (self.qconv and torch.cuda.is_available()) else None
         self.model = model
-        if fuse_bn:      # fold BN into the site kernels where shapes allow (training, 64 < batch <= 128); no-op otherwise
-            for m in model.modules():
-                if hasattr(m, "fuse_bn"):
-                    m.fuse_bn = True
         self.defer_losses = defer_losses
         self._deferred = DeferredLosses() if (defer_losses and torch.cuda.is_available()) else None
         named = list(model.named_parameters())
@@ -558,23 +554,19 @@ class OfficeTrainStep(_CapturedStep):
         # matrix cores, csrc/qgemm_kernels.hip) instead of MIOpen's fp32 kernels (the 7x7 stem included: alignq_qconv_stem7_*).  Their filter
         # gradients leave split-K slabs that one reduction launch per 32 filters finishes (fused.DeferredWgrads).
         self.qconv = bool(qconv and channels_last and torch.cuda.is_available())
-        for mod in model.modules():
-            if hasattr(mod, "quantize_fn"):
-                mod.use_qconv = self.qconv
-                # every Conv2d_Q of this network is followed by a batch-norm; folded (fuse_bn) it reads the convolution's
-                # per-tile statistics instead of making a pass of its own over the output
-                mod.emit_bn_stats = bool(self.qconv and fuse_bn and fuse_relu)
+        paths.apply(
+            model,
+            use_qconv=self.qconv,
+            # every Conv2d_Q of this network is followed by a batch-norm; folded (fuse_bn) it reads the convolution's
+            # per-tile statistics instead of making a pass of its own over the output
+            emit_bn_stats=bool(self.qconv and fuse_bn and fuse_relu),
+            # pack_bins (N2; with qconv and fuse_bn): relu(act_q1(bn1(.))) and relu(act_q2(bn2(.))) of every bottleneck
+            # feed conv2 / conv3 only - they are stored as int16 level indices (no fp32 copy): the quantiser writes, the
+            # convolution's forward and filter gradient read 2 B per element instead of 4
+            pack_bins=bool(pack_bins and self.qconv and fuse_bn and fuse_relu),
+            fuse_relu=bool(fuse_relu),
+            fuse_bn=bool(fuse_bn and fuse_relu and channels_last))
         self._wgrads = DeferredWgrads() if self.qconv else None
-        # pack_bins (N2; with qconv and fuse_bn): relu(act_q1(bn1(.))) and relu(act_q2(bn2(.))) of every bottleneck feed
-        # conv2 / conv3 only - they are stored as int16 level indices (no fp32 copy): the quantiser writes, the convolution's
-        # forward and filter gradient read 2 B per element instead of 4
-        for mod in model.modules():
-            if hasattr(mod, "act_q1") and hasattr(mod, "act_q2") and hasattr(mod, "act_q3"):
-                mod.pack_bins = bool(pack_bins and self.qconv and fuse_bn and fuse_relu)
-        for mod in model.modules():
-            if hasattr(mod, "act_q0") or (hasattr(mod, "act_q1") and hasattr(mod, "act_q2") and hasattr(mod, "act_q3")):
-                mod.fuse_relu = bool(fuse_relu)
-                mod.fuse_bn = bool(fuse_bn and fuse_relu and channels_last)
         self.dual = bool(fuse_bn and fuse_relu and channels_last) if dual is None else bool(dual)
         self.model, self.alpha = model, alpha
         named = list(model.named_parameters())

@@ -339,8 +339,8 @@ def block_strides(cfg):
 
 
 def state_bits(net):
-    flags = {(n, f): m.__dict__.get(f, "<absent>") for n, m in net.named_modules()
-             for f in ("fuse_bn", "fuse_relu", "use_qconv", "emit_bn_stats", "pack_bins", "_wq_stage")}
+    from alignq_amd.paths import FLAGS
+    flags = {(n, f): m.__dict__.get(f, "<absent>") for n, m in net.named_modules() for f in FLAGS}
     return ({k: v.detach().clone() for k, v in net.state_dict().items()}, {n: m.training for n, m in net.named_modules()}, flags)
 
 

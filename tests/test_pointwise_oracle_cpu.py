@@ -219,12 +219,15 @@ def test_refusals_before_any_launch():
 
 
 def test_default_is_off_and_the_opt_in_sets_one_attribute():
-    """mobilenet.use_hip_convs(model) leaves no `use_qconv_pw` anywhere; pointwise=True sets it on every Conv2d_Q"""
+    """mobilenet.use_hip_convs(model) leaves `use_qconv_pw` at Conv2d_Q's class default, off, in no instance and on no other kind of
+    module; pointwise=True sets it on every Conv2d_Q"""
     from alignq_amd import mobilenet as M
     torch.manual_seed(0)
     net = M.use_hip_convs(M.mobile_v2(4, 4, "second"))
     convs = [m for m in net.modules() if hasattr(m, "quantize_fn")]
-    assert convs and all(m.use_qconv for m in convs) and not any(hasattr(m, "use_qconv_pw") for m in net.modules())
+    assert convs and all(m.use_qconv for m in convs)
+    assert all(m.use_qconv_pw is False and "use_qconv_pw" not in m.__dict__ for m in convs)
+    assert not any(hasattr(m, "use_qconv_pw") for m in net.modules() if not hasattr(m, "quantize_fn"))
     net = M.use_hip_convs(net, pointwise=True)
     assert all(m.use_qconv_pw is True for m in convs)
     assert not any(hasattr(m, "use_qconv_pw") for m in net.modules() if not hasattr(m, "quantize_fn"))
