@@ -238,8 +238,9 @@ PLAIN = (
     # 64 < B <= 128: site_bwd4_kernel<32> (F < 16384), <64> (F >= 16384), the looped <64> form (B = 128, 513 tiles over 256
     # workgroups: trip counts 3 and 2), and the scalar-access path (F % 4 != 0)
     + [("bwd4", B, F) for B in (65, 100, 128) for F in (96, 4096, 8192, 16384, 32832, 4098)]
-    # B > 128: the pair kernels of the blocked Gram
-    + [("large", 130, 70), ("large", 192, 384), ("large", 513, 72)]
+    # B > 128: the pair kernels of the blocked Gram: corrl_bwd_kernel<2, 4, true> (up to 256 rows), <4, 4, true> (up to 512: 300),
+    # <4, 8, true> (above)
+    + [("large", 130, 70), ("large", 192, 384), ("large", 300, 72), ("large", 513, 72)]
 )
 # folded batch-norm forms, (B, C, H): channel count C, H x H pixels
 BN4 = ((128, 16, 16), (100, 32, 16), (128, 64, 8))          # 64 < B <= 128: site_bwd4_kernel<TF, true, true>

@@ -155,8 +155,10 @@ def _expected_y(x, k, r, res, relu):
 @pytest.mark.parametrize("nhwc", [0, 1])
 def test_bn_folded_site_kernels_vs_oracle(dev, nhwc, B, C, H, k):
     """site_fwd4_kernel<TF,true> / site_bwd4_kernel<TF,true,true> / bn_bwd_apply at the ResNet-20/56 site shapes
-    128 x {16384, 8192, 4096}, both layouts, against the C oracle; F = 36864 and 32768 (a short batch) run the forward's
-    multi-tile instantiation (more tiles than workgroups: accumulators carried over the tile loop)."""
+    128 x {16384, 8192, 4096}, both layouts, against the C oracle; F = 36864 runs the forward's multi-tile instantiation (576
+    tiles on 512 workgroups: accumulators carried over the tile loop).  F = 32768 (at a short batch of 100) does NOT: geom() gives
+    512 tiles on a 512-workgroup grid and launch_fwd4_tf takes the one-tile branch (tests/test_site_fwd_oracle_cpu.py pins both);
+    what that shape adds is the 64-feature one-tile form with masked rows."""
     if F_big := (C * H * H > 16384):
         if k == 4 and not nhwc:
             pytest.skip("k = 4 at the large shapes runs in the channels-last layout only (oracle time)")

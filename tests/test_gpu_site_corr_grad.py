@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from tests import oracle_c as O
+from tests import site_fwd_oracle as SF
 from tests import site_grad_oracle as G
 from tests.test_gpu_bench_path import _SiteRun, _dev_like, _mem
 
@@ -111,7 +112,8 @@ PLAIN_ROWS = list(G.PLAIN) + [("bwd4+4bytes", B, 4096) for B in (65, 100, 128)]
 def test_plain_site_correlation_gradient(dev, form, B, F):
     """launch_bwd1 (B <= 32), site_bwd_kernel<2, true> (B <= 64), site_bwd4_kernel<32 | 64 | looped 64> (B <= 128) and the
     blocked pair kernels (B > 128): explicit dD with no g (ops.SiteDFn), explicit dD with g (ops.SiteLargeFn: alignq_site_fwd /
-    alignq_site_bwd at any B), and up to 128 rows the rebuilt form (ops.SiteFn: alignq_site_bwd_fused, dD_scale = B^2)."""
+    alignq_site_bwd at any B; the D it returns is held to the forward's own bar, tests/site_fwd_oracle.py), and up to 128 rows the
+    rebuilt form (ops.SiteFn: alignq_site_bwd_fused, dD_scale = B^2)."""
     from alignq_amd import ops
     x0, dD0 = G.plain_inputs(B, F)
     eps = G.plain_eps(B)
@@ -140,6 +142,13 @@ def test_plain_site_correlation_gradient(dev, form, B, F):
     xt = leaf()
     xq, D = ops.SiteLargeFn.apply(xt, K, R, eps)
     torch.autograd.backward([xq, D], [cu(g0, dev), cu(dD0, dev)])
+    # the forward's D at ITS own scale (tests/site_fwd_oracle.py): BAR * s_ij of the form this shape selects
+    fname = SF.form(B, F, False, not form.endswith("+4bytes"))
+    t0 = SF.transform(x0)
+    fref = SF.reference(x0, t0, eps)
+    d_err = np.abs(npy(D).astype(np.float64) - fref["D"]) / SF.d_bar(fname, fref, SF.cond_allowance(x0, t0, eps, SF.acc_of(B)))
+    print(f"[site-corr-grad] {form} {B}x{F} forward D ({fname}): worst error / bar = {float(d_err.max()):.3f}")
+    assert d_err.max() <= 1.0, (form, B, F, fname, float(d_err.max()))
     check_sum(f"{form} {B}x{F} explicit dD", npy(xt.grad), ref, g0.astype(np.float64) * G.jac(x0, R), term)
 
     if B > 128:
