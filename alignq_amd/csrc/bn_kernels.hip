@@ -351,7 +351,7 @@ int alignq_bn_bwd_totals(const float* dx_part, int B, int C, int HW, float* ktot
 
 int alignq_bn_bwd_apply(const float* dx, const float* z, const float* ab, const float* save, const float* dx_part, int B,
                         int C, int HW, int nhwc, float* dz, float* dgamma, float* dbeta, void* stream) {
-  if (!dx || !z || !ab || !save || !dx_part || !dz || B < 1 || C < 1) return ALIGNQ_EINVAL;
+  if (!dx || !z || !ab || !save || !dx_part || !dz || B < 1 || C < 1 || HW < 1) return ALIGNQ_EINVAL;
   if (nhwc) {
     if (!nhwc_channels_ok(C)) return ALIGNQ_EUNSUPPORTED;
     const int64_t F = (int64_t)C * HW;

@@ -656,6 +656,12 @@ int alignq_site_bwd_apply_bn_fill(const float* g, const float* S, const float* z
                                   float* dresidual, const float* stats, int B, int64_t F, float act_range, float eps,
                                   float* dx, float* dx_part, int n_fill, const void* const* fill_ws, float* const* fill_dw,
                                   const int* fill_n_slabs, const int* fill_n_elem, void* stream);
+/* Refusals of the stand-alone batch-norm entries (nothing is launched, no output is touched):
+ * ALIGNQ_EINVAL: a NULL required pointer (dgamma / dbeta, and alignq_bn_stats' gamma / beta / running statistics / counter, are
+ *   optional), B < 1, C < 1, HW < 1 (HW < 4 for alignq_bn_partial_stats / alignq_bn_stats);
+ * ALIGNQ_EUNSUPPORTED: NCHW statistics with HW % 4 != 0 or a z that is not 16-byte aligned; the NCHW backward with HW % 64 != 0;
+ *   channels-last with C not a power of two in [4,256], a z that is not 16-byte aligned (statistics), or C * HW not a multiple of
+ *   the backward tile (64 features from C * HW = 16384, else 32).                                                            */
 int alignq_bn_bwd_apply(const float* dx, const float* z, const float* ab, const float* save, const float* dx_part, int B,
                         int C, int HW, int nhwc, float* dz, float* dgamma, float* dbeta, void* stream);
 /* Channels-last (torch.channels_last, memory [B,H,W,C]) form of the fold, nhwc = 1 above: channel = f mod C with C a power

@@ -244,6 +244,12 @@ PLAIN = (
 )
 # folded batch-norm forms, (B, C, H): channel count C, H x H pixels
 BN4 = ((128, 16, 16), (100, 32, 16), (128, 64, 8))          # 64 < B <= 128: site_bwd4_kernel<TF, true, true>
+# the same kernels at the channel counts and partial forms the fold admits beyond those three (bn_shape_ok: channels-last at any
+# power-of-two C in [4, 256] with F % 64 == 0, NCHW at any C with HW % 64 == 0), (B, C, HW) with HW not a square; what each row selects:
+# tests/test_gpu_bn_forms.py.  Lists of their own: the BN4 test asserts filler slots that the large rows do not have.
+BN4_CL = ((65, 4, 16), (128, 8, 8), (100, 64, 1), (128, 256, 1), (65, 128, 33), (100, 4, 1040), (128, 256, 64), (128, 256, 129))
+BN4_NCHW = ((65, 1, 64), (128, 3, 128), (100, 5, 832), (128, 3, 11008))
+BN4_HARD = {1: (128, 8, 8), 0: (128, 3, 128)}               # per layout: the row that also runs with a channel of mean 30, std 0.5
 BN1 = ((6, 64, 4), (28, 256, 2))                            # B <= 32: the site1 groups kernels (channels-last)
 AB1 = (28, 64, 4)                                           # alignq_site_bwd_apply_ab[_relu]
 
@@ -263,10 +269,10 @@ def plain_inputs(B, F):
     return x, dD
 
 
-def bn_inputs(B, C, H, seed=0):
-    """z [B, C*H*H] in memory order, gamma, beta, a non-symmetric dD."""
+def bn_inputs(B, C, H, seed=0, HW=None):
+    """z [B, C*H*H] (C*HW where HW is given: H only seeds then) in memory order, gamma, beta, a non-symmetric dD."""
     rng = np.random.default_rng(1009 * B + 31 * C + H + seed)
-    F = C * H * H
+    F = C * (H * H if HW is None else HW)
     z = (rng.standard_normal((B, F)) * 1.7 + 0.3).astype(np.float32)
     gamma = (rng.random(C) + 0.5).astype(np.float32)
     beta = (rng.standard_normal(C) * 0.2).astype(np.float32)

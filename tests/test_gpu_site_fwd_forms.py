@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import bn_oracle as N
 from tests import oracle_c as O
 from tests import site_fwd_oracle as S
 from tests import site_grad_oracle as G
@@ -320,6 +321,13 @@ def test_folded_site_forward(dev, B, C, H, nhwc):
     ab_k = out["ab"].reshape(2, C)
     np.testing.assert_allclose(ab_k, ab_o, rtol=3e-6, atol=1e-7)
     np.testing.assert_allclose(out["save"].reshape(2, C), save_o, rtol=3e-6, atol=1e-7)
+    # and against float64 at the bars derived from the arithmetic (tests/bn_oracle.py: 1.4 to 55 times tighter than the line above at these inputs)
+    ref = N.forward(zm, C, nhwc, gamma, beta)
+    nbar = N.fwd_bars(ref, invstd_fp32=bool(nhwc))
+    sv = out["save"].reshape(2, C)
+    w = [N.worst(got, ref[n], nbar[n]) for got, n in ((ab_k[0], "a"), (ab_k[1], "b"), (sv[0], "mean"), (sv[1], "invstd"))]
+    print(f"[site-fwd] {tag} a, b, mean, invstd: worst error / derived bar = " + " ".join(f"{v:.3f}" for v in w))
+    assert max(w) <= 1.0, (tag, w)
     h, bar = check_fold(tag + " finalised from the statistics kernel", name, zm, C, nhwc, ab_k, out, K, False, None, hosts)
     check_scal(tag, h, bar, out["scal"], f.A0, f.G0)
     for k in (4, 8):
