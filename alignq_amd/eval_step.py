@@ -71,29 +71,34 @@ class EvalStep(_CapturedStep):
     def _quantize_weights(self):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
         evaluation refreshes the SAME tensors in place: a captured graph keeps reading them."""
-        convs = [c for c in self.all_convs if getattr(c.quantize_fn, "w_bit", 32) != 32 and hasattr(c.quantize_fn, "_pre")]
+        convs = [c for c in self.all_convs
+                 if getattr(c.quantize_fn, "w_bit", 32) != 32 and getattr(c.quantize_fn, "parks_filters", False)]
         if self._packed is not None:
-            # from the packed codes (alignq_weight_unpack_multi) into tensors that persist: (weight, q, no cdf, no pdf, bins, image)
-            outs = self._packed.refresh(pack=self._pack_filters(), images=self.filter_images)
-            if self._wq is None or any(self._wq.get(id(c), (None, None))[1] is not outs[id(c)][0] for c in convs):
+            # from the packed codes (alignq_weight_unpack_multi) into tensors that persist (records without cdf and pdf)
+            fresh = self._packed.refresh(pack=self._pack_filters(), images=self.filter_images)
+            if self._wq is None or any(id(c) not in self._wq or self._wq[id(c)].q is not fresh[id(c)].q for c in convs):
                 self._graph = None
-            self._wq = {id(c): (c.weight, outs[id(c)][0], None, None, outs[id(c)][1], outs[id(c)][2]) for c in convs}
-            for c in convs:
-                c.quantize_fn._pre = self._wq[id(c)]
-                c.quantize_fn._pre_keep = True
-            return
-        fused.prequantize_weights(convs, pack=self._pack_filters(), images=self.filter_images)
-        fresh = {id(c): c.quantize_fn._pre for c in convs}
-        if self._wq is not None and set(self._wq) == set(fresh):
-            for key, old in self._wq.items():
-                for o, n in zip(_flat(old[1:]), _flat(fresh[key][1:])):
-                    o.copy_(n)
+            self._wq = {id(c): fresh[id(c)] for c in convs}
         else:
-            self._wq = fresh
-            self._graph = None           # (tensors a captured graph read are gone)
+            fused.prequantize_weights(convs, pack=self._pack_filters(), images=self.filter_images)
+            fresh = {id(c): c.quantize_fn.parked for c in convs}
+            # (in place only into records of the same make-up: the same convolutions, each with bins / an image then and now)
+            if (self._wq is not None and set(self._wq) == set(fresh)
+                    and all((o is None) == (n is None) for key in fresh for o, n in zip(self._wq[key], fresh[key]))):
+                for key, old in self._wq.items():
+                    new = fresh[key]
+                    old.q.copy_(new.q)
+                    old.cdf.copy_(new.cdf)
+                    old.pdf.copy_(new.pdf)
+                    for o, n in zip(old.bins or (), new.bins or ()):     # the (bf16, f16) pair
+                        o.copy_(n)
+                    if old.image is not None:
+                        old.image.copy_(new.image)
+            else:
+                self._wq = fresh
+                self._graph = None           # (tensors a captured graph read are gone)
         for c in convs:
-            c.quantize_fn._pre = self._wq[id(c)]
-            c.quantize_fn._pre_keep = True
+            c.quantize_fn.park(self._wq[id(c)], keep=True)
 
     def begin(self):
         if self._saved is not None:
@@ -119,9 +124,8 @@ class EvalStep(_CapturedStep):
 
     def end(self):
         for c in self.all_convs:
-            q = c.quantize_fn
-            if hasattr(q, "_pre"):
-                q._pre, q._pre_keep = None, False
+            if getattr(c.quantize_fn, "parks_filters", False):
+                c.quantize_fn.unpark()
         flags, modes = self._saved or ((), ())
         paths.restore(flags)
         for m, training in modes:
@@ -209,11 +213,3 @@ class EvalStep(_CapturedStep):
         if n == 0:
             return float("nan"), 0.0, 0.0, 0
         return ce / n, 100.0 * n1 / n, 100.0 * n5 / n, n
-
-
-def _flat(items):
-    for t in items:
-        if isinstance(t, (tuple, list)):
-            yield from _flat(t)
-        elif torch.is_tensor(t):
-            yield t

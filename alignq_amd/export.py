@@ -45,9 +45,10 @@ def _stream_fits(f):
 
 
 def quantised_convs(model):
-    """[(state_dict key of the filter, module)] of the Conv2d_Q modules whose filters are quantised (w_bit < 32), in module order"""
+    """[(state_dict key of the filter, module)] of the Conv2d_Q modules whose filters are quantised (w_bit < 32) by a quantiser that
+    takes parked filters (weight_quantize_fn.parks_filters), in module order"""
     return [(name + ".weight", m) for name, m in model.named_modules()
-            if hasattr(m, "quantize_fn") and getattr(m.quantize_fn, "w_bit", 32) != 32 and hasattr(m.quantize_fn, "_pre")]
+            if hasattr(m, "quantize_fn") and getattr(m.quantize_fn, "w_bit", 32) != 32 and getattr(m.quantize_fn, "parks_filters", False)]
 
 
 def admm_keys(model):
@@ -194,7 +195,7 @@ def pack_model(model, keep_admm=False):
         fused.prequantize_weights(convs)
         try:
             for (k, formula), members in groups.items():
-                qs = [c.quantize_fn._pre[1].detach() for _, c in members]
+                qs = [c.quantize_fn.parked.q.detach() for _, c in members]
                 codes, bad = pack_codes(qs, k, formula)
                 if bad:
                     culprits = []
@@ -209,7 +210,7 @@ def pack_model(model, keep_admm=False):
                                      "bits": code_bits(k, formula)}
         finally:
             for c in convs:
-                c.quantize_fn._pre = None
+                c.quantize_fn.unpark()
     drop = set(filters) | (set() if keep_admm else admm_keys(model))
     rest = {k: v.detach().clone() for k, v in model.state_dict().items() if k not in drop}
     meta = {"format": FORMAT, "version": FORMAT_VERSION, "act_range": float(config.args.act_range)}
@@ -238,11 +239,11 @@ class PackedFilters:
             raise ValueError("EvalStep(weights=): " + "; ".join(problems))
         self.pk = pk
         self.codes = None        # per conv, on the device
-        self.out = None          # id(conv) -> (q, bins or None, image or None)
+        self.out = None          # id(conv) -> (q, bins or None, (image, its geometry) or None)
 
     def refresh(self, pack, images):
         """Unpack every filter (one call per (w_bit, formula) group) into tensors that stay the same across calls; returns
-        {id(conv): (q, bins, image)}."""
+        {id(conv): fused.QuantizedFilter(conv.weight, q, bins=, image=)} (no cdf, no pdf)."""
         from . import fused
         lib = L.load()
         dev = self.named[0][1].weight.device if self.named else None
@@ -269,4 +270,8 @@ class PackedFilters:
                            qs=[o[0] for o in outs],
                            bins_bf16=[o[1][0] if o[1] else None for o in outs], bins_f16=[o[1][1] if o[1] else None for o in outs],
                            images=[o[2][0] if o[2] else None for o in outs], geoms=[o[2][1] if o[2] else None for o in outs])
-        return {key: (q, bins, image[0] if image else None) for key, (q, bins, image) in self.out.items()}
+        recs = {}
+        for _, c in self.named:
+            q, bins, image = self.out[id(c)]
+            recs[id(c)] = fused.QuantizedFilter(c.weight, q, bins=bins, image=image[0] if image else None)
+        return recs

@@ -1,9 +1,9 @@
 """Whole-model fast paths that keep the reference's per-module API intact (all opt-in; TrainStep switches them on).
 
 * `prequantize_weights(convs)` / `WeightQuantAllFn`: ALL conv weights of a model quantised with two multi-tensor launches
-  (alignq_weight_quant_fwd_multi) instead of four launches per tensor; results are parked in each `conv.quantize_fn` and
-  consumed by the next `weight_quantize_fn.forward(conv.weight)`.  The backward is again two multi-tensor launches (and
-  first finishes any deferred filter-gradient reductions).
+  (alignq_weight_quant_fwd_multi) instead of four launches per tensor; each result is parked in its `conv.quantize_fn` as a
+  `QuantizedFilter` record (weight_quantize_fn.park) and consumed by the next `weight_quantize_fn.forward(conv.weight)`.  The
+  backward is again two multi-tensor launches (and first finishes any deferred filter-gradient reductions).
 * `DeferredLosses` / `LossSumFn` / `SiteRecord`: every ADMM site's slab reduction + loss in ONE launch after the last layer,
   every site's backward prep in ONE launch.
 * `BNSiteFn` / `bn_site`: `act_q(bn(z)) [+ residual] [-> relu]` with the batch-norm folded into the site kernels (NCHW or
@@ -24,12 +24,9 @@ from . import _lib as L
 
 class WeightQuantAllFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, k, formula, *weights):
-        # a trailing non-tensor argument: per-weight filter-image buffers (uint8 tensors or None, see filter_image_geometry),
-        # written by the same launch (alignq_weight_quant_fwd_multi_img)
-        images = None
-        if weights and isinstance(weights[-1], (list, tuple)):
-            images, weights = weights[-1], weights[:-1]
+    def forward(ctx, k, formula, images, *weights):
+        # images: None, or per-weight filter-image buffers (uint8 tensors or None, see filter_image_geometry), written by the same
+        # launch (alignq_weight_quant_fwd_multi_img)
         lib = L.load()
         ws_ = [L.dense_f32(w, "weight") for w in weights]
         T = len(ws_)
@@ -74,7 +71,7 @@ class WeightQuantAllFn(torch.autograd.Function):
         L.check(lib.alignq_weight_quant_bwd_multi(T, L.ptr_array(gs), L.ptr_array(list(ws_)), L.ptr(ms),
                                                   L.ptr_array(dws), L.i64_array([w.numel() for w in ws_]),
                                                   L.ptr(scratch), L.stream_ptr()), "alignq_weight_quant_bwd_multi")
-        return (None, None) + tuple(dws) + ((None,) if len(ctx.needs_input_grad) > 2 + T else ())
+        return (None, None, None) + tuple(dws)
 
 
 def filter_image_geometry(w):
@@ -98,8 +95,9 @@ def prequantize_weights(convs, pack=False, images=False):
     pack: also leave every (<= 8-bit) filter's integer bins as bf16 / f16 bit patterns (ops.pack_filter_bins, one launch per 64
     filters) for the GEMM convolutions of ops.QConvGemmFn.
     images: the quantiser's own launch also writes the bf16 filter images of every `use_qconv` module whose geometry the
-    convolution kernels read images for (filter_image_geometry); parked as the sixth field of `_pre`, handed out by
-    weight_quantize_fn.take_image."""
+    convolution kernels read images for (filter_image_geometry).
+    Each module's quantiser gets its QuantizedFilter parked (weight_quantize_fn.park); the convolution reads the bins and the
+    image of the filter its quantiser returned through weight_quantize_fn.filter_of."""
     convs = [c for c in convs if c.quantize_fn.w_bit != 32]
     if not convs:
         return
@@ -117,10 +115,7 @@ def prequantize_weights(convs, pack=False, images=False):
                             torch.empty(lib.alignq_filter_image_bytes(*geo[:3]), dtype=torch.uint8, device=c.weight.device))
             if all(im is None for im in imgs):
                 imgs = None
-        if imgs is not None:
-            outs = WeightQuantAllFn.apply(k, formula, *[c.weight for c in cs], imgs)
-        else:
-            outs = WeightQuantAllFn.apply(k, formula, *[c.weight for c in cs])
+        outs = WeightQuantAllFn.apply(k, formula, imgs, *[c.weight for c in cs])
         T = len(cs)
         bins = None
         if pack and 1 <= k <= 8:
@@ -129,10 +124,9 @@ def prequantize_weights(convs, pack=False, images=False):
             packed = ops.pack_filter_bins([outs[i].detach() for i in sel], k)
             bins = dict(zip(sel, packed))
         for i, c in enumerate(cs):
-            pre = (c.weight, outs[i], outs[T + i], outs[2 * T + i])
-            b = bins[i] if bins is not None and i in bins else None
-            im = imgs[i] if imgs is not None else None
-            c.quantize_fn._pre = pre + ((b, im) if im is not None else (b,) if b is not None else ())
+            c.quantize_fn.park(QuantizedFilter(c.weight, outs[i], outs[T + i], outs[2 * T + i],
+                                               bins=bins.get(i) if bins is not None else None,
+                                               image=imgs[i] if imgs is not None else None))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -403,6 +397,19 @@ class LazyLink:
 
 
 _posted_links = []
+
+
+class QuantizedFilter(typing.NamedTuple):
+    """What the weight quantiser hands to the convolution that reads the filter (weight_quantize_fn.park / filter_of): `q`, cdf and
+    pdf are the quantiser's three outputs for the tensor `weight`.  bins: the (bf16, f16) bit patterns of q's integer bins for the
+    GEMM convolutions (ops.pack_filter_bins), None: the convolution packs them itself.  image: q's pre-packed bf16 filter images (a
+    uint8 tensor, filter_image_geometry), None: the convolution reads the fp32 filter."""
+    weight: typing.Any
+    q: typing.Any
+    cdf: typing.Any = None
+    pdf: typing.Any = None
+    bins: typing.Any = None
+    image: typing.Any = None
 
 
 class ConvStats(typing.NamedTuple):
@@ -1209,7 +1216,7 @@ def site_eval_twin(bnA, actA, zA, bnB, actB, zB, clampB):
 
 def dw_site_eval(conv, bn, act, x, clamp):
     """clamp(act(bn.eval()(conv(x)))) for a depthwise 3x3 Conv2d_Q by one alignq_dwconv3x3_site_eval_fwd launch: the expanded tensor
-    between the convolution and its site is never written.  The filter is the one EvalStep parked in conv.quantize_fn._pre (the
+    between the convolution and its site is never written.  The filter is the one EvalStep parked in conv.quantize_fn (the
     weight itself at w_bit == 32).  None where the depthwise kernels do not apply, `use_qconv` is off or no filter is parked."""
     from . import config, ops
     if not (conv.use_qconv and _nhwc_f32(x)):
@@ -1218,10 +1225,10 @@ def dw_site_eval(conv, bn, act, x, clamp):
     if getattr(q, "w_bit", 32) == 32:
         wq = conv.weight
     else:
-        pre = getattr(q, "_pre", None)
-        if pre is None or pre[0] is not conv.weight:
+        parked = q.parked
+        if parked is None or parked.weight is not conv.weight:
             return None
-        wq = pre[1]
+        wq = parked.q
     if not ops.qconv_dw_supported(x, wq, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, q.w_bit):
         return None
     B, C, H, W = x.shape

@@ -619,12 +619,12 @@ class QConv3x3Fn(torch.autograd.Function):
     instead of by a separate accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, tap=False, _unused=False, xbins=None, a_bit=0, img=None, part=None, link=None):
-        """img: the filter's pre-packed bf16 images (weight_quantize_fn.take_image; a uint8 tensor written by the quantiser's launch
-        from this w): forward and data gradient read them in place of w (alignq_conv3x3_nhwc_img, bit-identical).
+    def forward(ctx, x, w, w_bit, tap=False, xbins=None, a_bit=0, img=None, part=None, link=None):
+        """img: the filter's pre-packed bf16 images (weight_quantize_fn.filter_of(w).image; a uint8 tensor written by the quantiser's
+        launch from this w): forward and data gradient read them in place of w (alignq_conv3x3_nhwc_img, bit-identical).
         part / link (apply_with_stats): the kernel's epilogue also leaves per-workgroup per-channel {sum y, sum y^2} in `part`
         (float [C, parts, 2]) for fused.bn_site, which then skips its own statistics pass over y and hands its lazy gradient back
-        through `link`.  (_unused keeps the positions behind it for callers that pass them by position.)
+        through `link`.
         xbins (N2): x is only a HANDLE (fused.packed_handle: shape and autograd edge, no data); the activation is read from its
         int8 / int16 level indices `xbins` (a_bit-bit ADMM-formula quantiser, ReLU already applied), forward and filter gradient."""
         B, C, H, W = x.shape
@@ -654,10 +654,10 @@ class QConv3x3Fn(torch.autograd.Function):
         B, C, H, W = x.shape
         n_parts = L.load().alignq_conv3x3_bn_parts(B, H, W, C)
         if n_parts <= 0:
-            return QConv3x3Fn.apply(x, w, w_bit, tap, False, xbins, a_bit, img)
+            return QConv3x3Fn.apply(x, w, w_bit, tap, xbins, a_bit, img)
         stats = _conv_stats(C, n_parts, 2 if (x.requires_grad and w.requires_grad) else int(x.requires_grad or w.requires_grad),
                             w.device)
-        out = QConv3x3Fn.apply(x, w, w_bit, tap, False, xbins, a_bit, img, stats.part, stats.link)
+        out = QConv3x3Fn.apply(x, w, w_bit, tap, xbins, a_bit, img, stats.part, stats.link)
         (out[0] if tap else out)._alignq_bn_part = stats
         return out
 
@@ -665,7 +665,7 @@ class QConv3x3Fn(torch.autograd.Function):
     def backward(ctx, gy, gtap=None):
         x, w = ctx.saved_tensors
         packed, a_bit, (B, C, H, W) = ctx.packed
-        nones = (None,) * 8
+        nones = (None,) * 7
         img = ctx.img
         if gy is None:                     # only the shortcut alias was used downstream
             return (gtap, None) + nones
@@ -934,11 +934,10 @@ class QConvGemmFn(torch.autograd.Function):
     integer bins from pack_filter_bins (None: packed here, one small launch).  xbins (N2): x is only a HANDLE (fused.packed_handle:
     shape and autograd edge); the activation is read from its int16 level indices `xbins`, forward and filter gradient.  The filter
     gradient's slab reduction is deferred to fused.DeferredWgrads when such a context is active.  part (apply_with_stats): the
-    epilogue's batch-norm partials, double [groups, parts, C_out, 2], filled by the forward launch (_unused keeps the positions
-    behind it for callers that pass them by position)."""
+    epilogue's batch-norm partials, double [groups, parts, C_out, 2], filled by the forward launch."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, stride, x_levels=0.0, groups=1, _unused=False, bins=None, xbins=None, part=None):
+    def forward(ctx, x, w, w_bit, stride, x_levels=0.0, groups=1, bins=None, xbins=None, part=None):
         B, CIN, H, W = x.shape
         COUT, ks = w.shape[0], w.shape[2]
         s = int(stride)
@@ -964,7 +963,7 @@ class QConvGemmFn(torch.autograd.Function):
         B, CIN, H, W = x.shape
         n_parts = L.load().alignq_qconv_bn_parts(B, H, W, CIN, w.shape[0], w.shape[2], int(stride), int(groups), float(x_levels))
         part = torch.empty(int(groups), n_parts, w.shape[0], 2, dtype=torch.float64, device=w.device)
-        y = QConvGemmFn.apply(x, w, w_bit, stride, x_levels, groups, False, bins, xbins, part)
+        y = QConvGemmFn.apply(x, w, w_bit, stride, x_levels, groups, bins, xbins, part)
         y._alignq_bnq_part = fused.ConvStatsQ(part, n_parts, int(groups))
         return y
 
@@ -993,7 +992,7 @@ class QConvGemmFn(torch.autograd.Function):
             xb = 2 if packed else 0
             _filter_grad(ws, dw, COUT * ks * ks * CIN, lambda dwp, nsp: L.check(lib.alignq_qconv_wgrad(
                 L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, CIN, COUT, ks, s, x_levels, xb, nsp, L.stream_ptr()), "alignq_qconv_wgrad"))
-        return (dx, dw) + (None,) * 8
+        return (dx, dw) + (None,) * 7
 
 
 def qconv_stem7_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
@@ -1014,11 +1013,11 @@ def qconv_stem7_supported(x, w, stride, padding, dilation, groups, bias, w_bit) 
 class QConvStem7Fn(torch.autograd.Function):
     """F.conv2d(image, weight_q, None, 2, 3) of the Office stem on alignq_qconv_stem7_fwd (csrc/qgemm_kernels.hip: the filter's integer
     bins times three exact bf16 terms of the image, gathered straight from global memory); batch-norm statistics of the output in
-    the epilogue (part and _unused: as QConvGemmFn's).  The image needs no gradient; the filter gradient is alignq_qconv_stem7_wgrad's (six leading term pairs,
+    the epilogue (part: as QConvGemmFn's).  The image needs no gradient; the filter gradient is alignq_qconv_stem7_wgrad's (six leading term pairs,
     deterministic slabs; their reduction is deferred to fused.DeferredWgrads when such a context is active)."""
 
     @staticmethod
-    def forward(ctx, x, w, w_bit, groups=1, _unused=False, bins=None, part=None):
+    def forward(ctx, x, w, w_bit, groups=1, bins=None, part=None):
         B, _, H, W = x.shape
         lib = L.load()
         if bins is None:
@@ -1036,7 +1035,7 @@ class QConvStem7Fn(torch.autograd.Function):
         B, _, H, W = x.shape
         n_parts = L.load().alignq_qconv_stem7_bn_parts(B, H, W, int(groups))
         part = torch.empty(int(groups), n_parts, 64, 2, dtype=torch.float64, device=w.device)
-        y = QConvStem7Fn.apply(x, w, w_bit, groups, False, bins, part)
+        y = QConvStem7Fn.apply(x, w, w_bit, groups, bins, part)
         y._alignq_bnq_part = fused.ConvStatsQ(part, n_parts, int(groups))
         return y
 
@@ -1053,7 +1052,7 @@ class QConvStem7Fn(torch.autograd.Function):
             ws = _ws(lib.alignq_qconv_stem7_wgrad_ws_bytes(B, H, W), w.device)
             _filter_grad(ws, dw, 64 * 147, lambda dwp, nsp: L.check(lib.alignq_qconv_stem7_wgrad(
                 L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, nsp, L.stream_ptr()), "alignq_qconv_stem7_wgrad"))
-        return (None, dw) + (None,) * 5
+        return (None, dw) + (None,) * 4
 
 
 def qconv_stem_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:

@@ -15,13 +15,14 @@ fallback.  Options the reference reads from its global `args` come from alignq_a
 from __future__ import annotations
 
 import types
+import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from . import config, ops
+from . import config, fused, ops
 
 _FORMULA = {"admm": L.FORMULA_ADMM, "office": L.FORMULA_ADMM, "cdf": L.FORMULA_CDF}
 _EPS = {"admm": 0.0, "office": 1e-5, "cdf": 0.0}
@@ -55,14 +56,30 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
             return ops.CdfFn.apply(x, m, s_, formula, float(kc), float(scale))
 
     class weight_quantize_fn(nn.Module):
+        parks_filters = True     # park() takes a fused.QuantizedFilter: EvalStep and export handle only such quantisers' filters
+
         def __init__(self, w_bit, stage):
             super().__init__()
             self.w_bit = w_bit
             self.stage = stage
             self.uniform_q = uniform_quantize(k=w_bit)
             self._formula = formula
-            self._pre = None      # (weight, q, cdf, pdf) parked by fused.prequantize_weights for the next call
-            self._pre_keep = False
+            self._parked = None     # the QuantizedFilter waiting for the next forward
+            self._keep = False
+            self._served = None     # (weak reference to the q the last forward returned, its bins, its image)
+
+        def park(self, record, keep=False):
+            """Leave a fused.QuantizedFilter for the next forward: called with `record.weight` itself it returns `record.q` and launches
+            nothing.  That forward consumes the record unless `keep` (EvalStep: the filters do not change over an evaluation), which
+            serves every forward until unpark()."""
+            self._parked, self._keep = record, bool(keep)
+
+        @property
+        def parked(self):
+            return self._parked
+
+        def unpark(self):
+            self._parked, self._keep = None, False
 
         def forward(self, x):
             if self.w_bit == 32:
@@ -70,17 +87,13 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                     self.weight_cdf = x
                     self.weight_q = x
                 return x
-            pre = self._pre
-            if not getattr(self, "_pre_keep", False):     # (EvalStep keeps the parked tensors for every batch of an evaluation: the filters do not change)
-                self._pre = None
-            self._bins = None
-            self._image = None
-            if pre is not None and pre[0] is x:
-                q, c, pdf = pre[1], pre[2], pre[3]
-                if len(pre) > 4 and pre[4] is not None:
-                    self._bins = (q.data_ptr(), pre[4])          # the filter's packed integer bins (fused.prequantize_weights(pack=True))
-                if len(pre) > 5 and pre[5] is not None:
-                    self._image = (q.data_ptr(), pre[5])         # its bf16 filter images (fused.prequantize_weights(images=True))
+            rec = self._parked
+            if not self._keep:
+                self._parked = None
+            self._served = None
+            if rec is not None and rec.weight is x:
+                q, c, pdf = rec.q, rec.cdf, rec.pdf
+                self._served = (weakref.ref(q), rec.bins, rec.image)     # (q only weakly: it carries the iteration's autograd history)
             else:
                 q, c, pdf = ops.WeightQuantFn.apply(x, self.w_bit, formula)
             if tree != "cdf":   # the CDF tree keeps these as locals (quantization.py:70-72)
@@ -92,16 +105,14 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 self._weight_cdf, self._weight_pdf = c, pdf
             return q
 
-        def take_bins(self, weight_q):
-            """(bf16, f16) bins of `weight_q` if the last forward left them (else None: the convolution packs them itself)."""
-            held = getattr(self, "_bins", None)
-            return held[1] if held is not None and held[0] == weight_q.data_ptr() else None
-
-        def take_image(self, weight_q):
-            """The filter images the quantiser's launch wrote with `weight_q` (a uint8 tensor), else None: the convolution then
-            reads the fp32 filter."""
-            held = getattr(self, "_image", None)
-            return held[1] if held is not None and held[0] == weight_q.data_ptr() else None
+        def filter_of(self, weight_q):
+            """A QuantizedFilter around `weight_q` (its `weight`, cdf and pdf are not kept) with the bins and the image a parked record
+            brought along, if `weight_q` is the very tensor object the last forward returned; for any other tensor - a copy, a hook's
+            replacement - a record without them: the convolution then packs the bins itself and reads the fp32 filter."""
+            served = self._served
+            if served is not None and served[0]() is weight_q:
+                return fused.QuantizedFilter(None, weight_q, bins=served[1], image=served[2])
+            return fused.QuantizedFilter(None, weight_q)
 
     def _plain_act(x, a_bit, stage):
         if a_bit == 32 and stage != "align":
@@ -271,6 +282,7 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 return self._conv(input, self.quantize_fn(self.weight))
 
             def _conv(self, input, weight_q):
+                rec = self.quantize_fn.filter_of(weight_q)     # the bins / image the quantiser holds for this very tensor, if any
                 packed = getattr(input, "_alignq_bins", None)
                 if packed is not None:
                     # N2: the input is a packed handle (fused.bn_site(pack=True)): its values are int8 / int16 level
@@ -280,18 +292,18 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                             and ops.qconv3x3_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
                                                              self.groups, self.bias, self.quantize_fn.w_bit)):
                         return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit,
-                                                               self.quantize_fn.take_image(weight_q))
+                                                               rec.image)
                     if (self.use_qconv and bins.dtype == torch.int16 and ops.level_count(input)
                             and ops.qconv_gemm_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
                                                                self.groups, self.bias, self.quantize_fn.w_bit)):
                         # the ResNet-50 shapes: the GEMM kernels read the int16 indices directly (forward and filter gradient)
-                        fb = self.quantize_fn.take_bins(weight_q)
+                        fb = rec.bins
                         if self.emit_bn_stats:
                             from . import fused
                             return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
                                                                     ops.level_count(input), fused.conv_groups(), fb, bins)
                         return ops.QConvGemmFn.apply(input, weight_q, self.quantize_fn.w_bit, self.stride[0], ops.level_count(input),
-                                                     1, False, fb, bins)
+                                                     1, fb, bins)
                     from . import fused
                     input = fused.materialize(input)
                 # opt-in: the convolutions on the matrix cores
@@ -301,32 +313,32 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):
                         return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit,
-                                                               img=self.quantize_fn.take_image(weight_q))
+                                                               img=rec.image)
                     if ops.qconv_gen_supported(*args):
                         return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0],
-                                                               img=self.quantize_fn.take_image(weight_q))
+                                                               img=rec.image)
                     if ops.qconv_stem_supported(*args):
                         return ops.QConvStemFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit)
                     if ops.qconv_stem7_supported(*args):     # the Office stem (7x7, stride 2, 3 -> 64 channels)
-                        bins = self.quantize_fn.take_bins(weight_q)
+                        bins = rec.bins
                         if self.emit_bn_stats:
                             from . import fused
                             return ops.QConvStem7Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, fused.conv_groups(), bins)
-                        return ops.QConvStem7Fn.apply(input, weight_q, self.quantize_fn.w_bit, 1, False, bins)
+                        return ops.QConvStem7Fn.apply(input, weight_q, self.quantize_fn.w_bit, 1, bins)
                     if ops.qconv_gemm_supported(*args):      # the ResNet-50 shapes: exact-product GEMMs (csrc/qgemm_kernels.hip)
-                        bins = self.quantize_fn.take_bins(weight_q)
+                        bins = rec.bins
                         if self.emit_bn_stats:     # the batch-norm behind this convolution takes its statistics
                             from . import fused                        # from the epilogue (fused.conv_partials)
                             return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
                                                                     ops.level_count(input), fused.conv_groups(), bins)
                         return ops.QConvGemmFn.apply(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
-                                                     ops.level_count(input), 1, False, bins)
+                                                     ops.level_count(input), 1, bins)
                     if ops.qconv_dw_supported(*args):        # MobileNet-V2's depthwise 3x3 (csrc/dwconv_kernels.hip)
                         return ops.QConvDwFn.apply(input, weight_q, self.stride[0])
                     # opt-in on top of use_qconv (mobilenet.use_hip_convs(model, pointwise=True)): the 1x1 convolutions whose channel
                     # counts are multiples of 8 (csrc/pointwise_kernels.hip); the multiples of 64 stay on the branch above
                     if self.use_qconv_pw and ops.qconv_pw_supported(*args):
-                        return ops.QConvPwFn.apply(input, weight_q, self.quantize_fn.w_bit, self.quantize_fn.take_bins(weight_q))
+                        return ops.QConvPwFn.apply(input, weight_q, self.quantize_fn.w_bit, rec.bins)
                 return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
             def forward_with_shortcut(self, input):
@@ -336,14 +348,15 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 is added inside the data-gradient kernel; otherwise plainly (forward(input), input)."""
                 weight_q = self.quantize_fn(self.weight)
                 if self.use_qconv and input.requires_grad:
+                    rec = self.quantize_fn.filter_of(weight_q)
                     args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
                             self.quantize_fn.w_bit)
                     if ops.qconv3x3_supported(*args):
                         return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, True,
-                                                               img=self.quantize_fn.take_image(weight_q))
+                                                               img=rec.image)
                     if ops.qconv_gen_supported(*args):      # transition block: the alias feeds the shortcut convolution
                         return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0], True,
-                                                               img=self.quantize_fn.take_image(weight_q))
+                                                               img=rec.image)
                 return self._conv(input, weight_q), input
 
         return Conv2d_Q

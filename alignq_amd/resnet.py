@@ -31,8 +31,8 @@ def _transition_pair(conv3, conv1, x):
     if not ops.transition_supported(conv3, conv1, x, conv3.weight, conv1.weight):
         return None
     w3, w1 = conv3.quantize_fn(conv3.weight), conv1.quantize_fn(conv1.weight)
-    return ops.QTransitionFn.apply_with_stats(x, w3, w1, conv3.quantize_fn.w_bit, conv3.quantize_fn.take_image(w3),
-                                              conv1.quantize_fn.take_image(w1))
+    return ops.QTransitionFn.apply_with_stats(x, w3, w1, conv3.quantize_fn.w_bit, conv3.quantize_fn.filter_of(w3).image,
+                                              conv1.quantize_fn.filter_of(w1).image)
 
 
 class PreActBlock_conv_Q(nn.Module):

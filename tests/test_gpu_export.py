@@ -370,8 +370,8 @@ def _packed_eval_equals_dense(dev, monkeypatch, tmp_path, make, x, y, want_bins,
     # one dequantised filter: logical shape, channels-last memory, the quantiser's values
     name, conv = export.quantised_convs(net)[1]
     fused.prequantize_weights([conv])
-    wq = conv.quantize_fn._pre[1].detach() + 0.0
-    conv.quantize_fn._pre = None
+    wq = conv.quantize_fn.parked.q.detach() + 0.0
+    conv.quantize_fn.unpark()
     deq = pk.dequantize(name)
     assert deq.shape == conv.weight.shape and deq.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(deq.view(torch.int32), wq.view(torch.int32))
@@ -383,16 +383,14 @@ def _packed_eval_equals_dense(dev, monkeypatch, tmp_path, make, x, y, want_bins,
     monkeypatch.setattr(export, "unpack_filters", lambda *a, **kw: (calls.__setitem__("unpack", calls["unpack"] + 1),
                                                                     real_unpack(*a, **kw))[1])
     qcls = type(named[0][1].quantize_fn)
-    real_bins, real_image = qcls.take_bins, qcls.take_image
+    real_filter_of = qcls.filter_of
 
-    def counting(real, key):
-        def take(self, wq_):
-            out = real(self, wq_)
-            calls[key] += out is not None
-            return out
-        return take
-    monkeypatch.setattr(qcls, "take_bins", counting(real_bins, "bins"))
-    monkeypatch.setattr(qcls, "take_image", counting(real_image, "images"))
+    def counting(self, wq_):
+        rec = real_filter_of(self, wq_)
+        calls["bins"] += rec.bins is not None
+        calls["images"] += rec.image is not None
+        return rec
+    monkeypatch.setattr(qcls, "filter_of", counting)
 
     ev = EvalStep(skeleton, weights=pk)
     with ev:
@@ -404,7 +402,7 @@ def _packed_eval_equals_dense(dev, monkeypatch, tmp_path, make, x, y, want_bins,
         assert graph is not None
         replayed = ev(x, y).clone()
         torch.cuda.synchronize()
-        parked = [c.quantize_fn._pre[1] for _, c in named]
+        parked = [c.quantize_fn.parked.q for _, c in named]
     assert torch.equal(got, want)
     assert torch.equal(replayed, want)
     if want_bins:
@@ -417,7 +415,7 @@ def _packed_eval_equals_dense(dev, monkeypatch, tmp_path, make, x, y, want_bins,
     with ev:
         assert calls["unpack"] == 2 and calls["prequantize"] == 0
         assert ev._graph is graph
-        assert all(c.quantize_fn._pre[1] is t for (_, c), t in zip(named, parked))
+        assert all(c.quantize_fn.parked.q is t for (_, c), t in zip(named, parked))
         again = ev(x, y).clone()
         assert ev.counts() == want_counts
     assert torch.equal(again, want)

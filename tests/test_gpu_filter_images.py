@@ -425,20 +425,27 @@ def test_eval_step_with_images_equals_without_and_builds_them_once(dev, monkeypa
             del calls[:]
             ev = EvalStep(model, channels_last=True, qconv=True, filter_images=on)
             with ev:
-                held = [c.quantize_fn._pre[5] if c.quantize_fn._pre is not None and len(c.quantize_fn._pre) > 5 else None
-                        for c in ev.all_convs]
-                assert sum(h is not None for h in held) == (20 if on else 0)
-                used = []
-                real_take = type(ev.all_convs[1].quantize_fn).take_image
-                monkeypatch.setattr(type(ev.all_convs[1].quantize_fn), "take_image",
-                                    lambda self, wq: (used.append(real_take(self, wq)), used[-1])[1])
+                held = {id(c.quantize_fn): c.quantize_fn.parked.image for c in ev.all_convs
+                        if c.quantize_fn.parked is not None and c.quantize_fn.parked.image is not None}
+                assert len(held) == (20 if on else 0)
+                used = []            # (quantiser, image) of every image a convolution was handed for its kernel
+                qcls = type(ev.all_convs[1].quantize_fn)
+                real_filter_of = qcls.filter_of
+
+                def spy(self, wq):
+                    rec = real_filter_of(self, wq)
+                    if rec.image is not None:
+                        used.append((id(self), rec.image))
+                    return rec
+                monkeypatch.setattr(qcls, "filter_of", spy)
                 logits[on] = [ev(x, y).clone() for x, y in zip(xs, ys)]
-                monkeypatch.setattr(type(ev.all_convs[1].quantize_fn), "take_image", real_take)
-                # both batches read the buffers the one quantiser launch of begin() wrote
+                monkeypatch.setattr(qcls, "filter_of", real_filter_of)
+                # both batches read the buffers the one quantiser launch of begin() wrote: each of the 20 convolutions once per batch
                 assert calls == [on]
-                assert len(used) == 2 * 20 and all((u is not None) == on for u in used)
+                assert len(used) == (2 * 20 if on else 0)
                 if on:
-                    assert {u.data_ptr() for u in used} == {h.data_ptr() for h in held if h is not None}
+                    assert sorted(q for q, _ in used) == sorted(2 * list(held))
+                    assert {im.data_ptr() for _, im in used} == {h.data_ptr() for h in held.values()}
             torch.cuda.synchronize()
         for a, b in zip(logits[True], logits[False]):
             assert torch.isfinite(a).all() and _same_bits(a.contiguous(), b.contiguous())

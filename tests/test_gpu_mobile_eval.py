@@ -452,7 +452,7 @@ def test_captured_replay_state_and_bare_forward(dev, monkeypatch, bits4):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     assert torch.equal(acc_cap, acc_eager)                             # the accumulator's 32 bytes
     assert same_state(before, state_bits(net))
-    assert all(c.quantize_fn._pre is None for c in ev.all_convs)
+    assert all(c.quantize_fn.parked is None for c in ev.all_convs)
     bare_after = bare_eval(net, xcl)
     assert torch.equal(bare_before.view(torch.int32), bare_after.view(torch.int32))
     d = (eager[0] - bare_before).abs().max().item()
@@ -479,7 +479,7 @@ def test_packed_weights_give_the_same_logits(dev, monkeypatch, bits4):
     with EvalStep(skeleton, weights=pk) as ev2:
         for name, c in export.quantised_convs(skeleton):
             if c.groups > 1:
-                assert c.quantize_fn._pre[1].shape == c.weight.shape and bool(torch.isfinite(c.quantize_fn._pre[1]).all())
+                assert c.quantize_fn.parked.q.shape == c.weight.shape and bool(torch.isfinite(c.quantize_fn.parked.q).all())
         got, cnt2 = ev2(x, y).clone(), ev2.counts()
     assert torch.isfinite(want).all()
     assert torch.equal(got.view(torch.int32), want.view(torch.int32)) and cnt == cnt2

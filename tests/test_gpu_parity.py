@@ -553,7 +553,7 @@ def test_prequantize_all_weights_matches_per_tensor(dev):
     gs = [torch.randn_like(c.weight) for c in convs]
     prequantize_weights(convs)
     qs = [c.quantize_fn(c.weight) for c in convs]
-    assert all(c.quantize_fn._pre is None for c in convs)
+    assert all(c.quantize_fn.parked is None for c in convs)
     sum((q * g).sum() for q, g in zip(qs, gs)).backward()
     for c, q, g in zip(convs, qs, gs):
         w2 = c.weight.detach().clone().requires_grad_(True)

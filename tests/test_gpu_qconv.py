@@ -230,7 +230,7 @@ def test_qconv_reads_int16_level_indices_bit_for_bit(dev, cin, cout, H, ks, stri
         w = wq.clone(memory_format=CL).requires_grad_(True)
         if packed:
             xin = fused.packed_handle(x.shape, dev).requires_grad_(True)
-            y = ops.QConvGemmFn.apply(xin, w, 8, stride, 255.0, 1, False, None, xb)
+            y = ops.QConvGemmFn.apply(xin, w, 8, stride, 255.0, 1, None, xb)
         else:
             xin = x.clone(memory_format=CL).requires_grad_(True)
             y = ops.QConvGemmFn.apply(xin, w, 8, stride, 255.0)
