@@ -34,6 +34,11 @@ CLAMP_NONE, CLAMP_RELU, CLAMP_RELU6 = (_MOBILE_CONSTANTS[n] for n in ("ALIGNQ_CL
 POINTWISE_SIGNATURES, _POINTWISE_STRUCTS, _POINTWISE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_pointwise.h"))
 PW_FWD, PW_DGRAD, PW_WGRAD = (_POINTWISE_CONSTANTS[n] for n in ("ALIGNQ_PW_FWD", "ALIGNQ_PW_DGRAD", "ALIGNQ_PW_WGRAD"))
 
+# K3CONV_SIGNATURES: the entry points of include/alignq_k3conv.h (the 3x3 / stride 1 Conv2d_Q convolutions at channel counts that
+# are multiples of 4), a fourth table, bound after the three above
+K3CONV_SIGNATURES, _K3CONV_STRUCTS, _K3CONV_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k3conv.h"))
+K3_FWD, K3_DGRAD, K3_WGRAD = (_K3CONV_CONSTANTS[n] for n in ("ALIGNQ_K3_FWD", "ALIGNQ_K3_DGRAD", "ALIGNQ_K3_WGRAD"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -81,6 +86,13 @@ def load():
         except AttributeError:
             raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_pointwise.h): it was built before "
                                      "csrc/pointwise_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
+        fn.restype, fn.argtypes = res, args
+    for name, (res, args) in K3CONV_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_k3conv.h): it was built before "
+                                     "csrc/k3conv_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib

@@ -1223,3 +1223,62 @@ class QConvPwFn(torch.autograd.Function):
             _filter_grad(ws, dw, COUT * CIN, lambda dwp, nsp: L.check(lib.alignq_pwconv_wgrad(
                 L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), M, CIN, COUT, nsp, L.stream_ptr()), "alignq_pwconv_wgrad"))
         return dx, dw, None, None
+
+
+def qconv_k3_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The 3x3 convolutions alignq_k3conv_* take (include/alignq_k3conv.h; DenseNet-40's dense layers): a (C_out, C_in, 3, 3)
+    channels-last filter, stride 1, padding 1, dilation 1, groups 1, no bias, <= 8-bit quantised filter, channels-last fp32 input,
+    C_in and C_out multiples of 4 in [4, 512]."""
+    if bias is not None or groups != 1 or not (1 <= w_bit <= 8):
+        return False
+    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1):
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and tuple(w.shape[1:]) == (x.shape[1], 3, 3)):
+        return False
+    if not w.is_contiguous(memory_format=torch.channels_last):
+        return False
+    B, CIN, H, W = x.shape
+    return L.load().alignq_k3conv_supported(B, H, W, CIN, w.shape[0]) == 1
+
+
+class QConvK3Fn(torch.autograd.Function):
+    """F.conv2d(input, weight_q, None, 1, 1) of Conv2d_Q.forward for a 3x3 filter at channel counts that are multiples of 4, on
+    alignq_k3conv_fwd / _dgrad / _wgrad (csrc/k3conv_kernels.hip): exact products of the filter's integer bins and three bf16 terms of
+    the fp32 operand.  bins: (bf16, f16) bit patterns of the filter's bins from pack_filter_bins (None: packed here, one small launch).
+    The filter gradient's slab reduction is deferred to fused.DeferredWgrads when such a context is active."""
+
+    @staticmethod
+    def forward(ctx, x, w, w_bit, bins=None):
+        B, CIN, H, W = x.shape
+        COUT = w.shape[0]
+        if bins is None:
+            bins = pack_filter_bins([w], w_bit)[0]
+        y = torch.empty((B, COUT, H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
+        L.check(L.load().alignq_k3conv_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B, H, W, CIN, COUT, int(w_bit), L.stream_ptr()),
+                "alignq_k3conv_fwd")
+        ctx.save_for_backward(x, w, bins[0])
+        ctx.w_bit = int(w_bit)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, wb = ctx.saved_tensors
+        B, CIN, H, W = x.shape
+        COUT = w.shape[0]
+        lib = L.load()
+        cl = torch.channels_last
+        if not gy.is_contiguous(memory_format=cl):
+            gy = gy.contiguous(memory_format=cl)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((B, CIN, H, W), dtype=torch.float32, device=w.device, memory_format=cl)
+            L.check(lib.alignq_k3conv_dgrad(L.ptr(gy), L.ptr(wb), L.ptr(dx), B, H, W, CIN, COUT, ctx.w_bit, L.stream_ptr()),
+                    "alignq_k3conv_dgrad")
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(w)
+            ws = _ws(lib.alignq_k3conv_wgrad_ws_bytes(B, H, W, CIN, COUT), w.device)
+            _filter_grad(ws, dw, COUT * 9 * CIN, lambda dwp, nsp: L.check(lib.alignq_k3conv_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, CIN, COUT, nsp, L.stream_ptr()), "alignq_k3conv_wgrad"))
+        return dx, dw, None, None
