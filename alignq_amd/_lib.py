@@ -39,6 +39,10 @@ PW_FWD, PW_DGRAD, PW_WGRAD = (_POINTWISE_CONSTANTS[n] for n in ("ALIGNQ_PW_FWD",
 K3CONV_SIGNATURES, _K3CONV_STRUCTS, _K3CONV_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k3conv.h"))
 K3_FWD, K3_DGRAD, K3_WGRAD = (_K3CONV_CONSTANTS[n] for n in ("ALIGNQ_K3_FWD", "ALIGNQ_K3_DGRAD", "ALIGNQ_K3_WGRAD"))
 
+# DENSE_SIGNATURES: the entry points of include/alignq_dense.h (DenseNet's evaluation without concatenations: a dense layer's site
+# inside its 3x3 convolution, the transition's pool written at a pitch), a fifth table, bound last
+DENSE_SIGNATURES, _DENSE_STRUCTS, _DENSE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_dense.h"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -53,6 +57,11 @@ class SiteBwdBnArgs(ctypes.Structure):
 class EvalSite(ctypes.Structure):
     """include/alignq_mobile.h: alignq_eval_site (one eval-mode batch-norm + quantiser + clamp)"""
     _fields_ = _MOBILE_STRUCTS["alignq_eval_site"]
+
+
+class DenseSite(ctypes.Structure):
+    """include/alignq_dense.h: alignq_dense_site (the eval-mode batch-norm + quantiser + clamp in front of a dense layer's convolution)"""
+    _fields_ = _DENSE_STRUCTS["alignq_dense_site"]
 
 
 _lib = None
@@ -93,6 +102,13 @@ def load():
         except AttributeError:
             raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_k3conv.h): it was built before "
                                      "csrc/k3conv_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
+        fn.restype, fn.argtypes = res, args
+    for name, (res, args) in DENSE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_dense.h): it was built before "
+                                     "csrc/dense_eval_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib

@@ -18,9 +18,11 @@
 #include "../../include/alignq.h"
 #include "../../include/alignq_mobile.h"
 #include "alignq_math.h"
+#include "eval_site_body.h"
 #include "store_forms.h"
 
 using namespace alignq;
+using namespace alignq_evalsite;      // SiteDev, ab_table, site_q, clamp4: eval_site_body.h (shared with dense_eval_kernels.hip)
 
 namespace {
 
@@ -36,12 +38,6 @@ constexpr int64_t kWtMinBytes = (int64_t)1 << 20, kWtMaxBytes = (int64_t)64 << 2
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-struct SiteDev {                           // alignq_eval_site as the kernels take it (by value)
-  const float *z, *gamma, *beta, *mean, *var;
-  float eps;
-  int k, clamp;
-};
-
 __device__ __forceinline__ float4 ld4_stream(const float4* p) {
   const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
@@ -51,49 +47,6 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4_out(float* p, const float4 v, const int wt) {
   if (wt) alignq_store::st16<alignq_store::kConvOut>(p, v);
   else *reinterpret_cast<float4*>(p) = v;
-}
-
-// the oracle's `v > 0 ? v : 0` (oq_bn_site_fwd): -0.0 and NaN both store +0.0; relu6 caps it at 6
-__device__ __forceinline__ float clamp1(float v, int clamp) {
-  if (clamp == ALIGNQ_CLAMP_NONE) return v;
-  const float hi = (clamp == ALIGNQ_CLAMP_RELU6 && !(v < 6.0f)) ? 6.0f : v;
-  return v > 0.0f ? hi : 0.0f;
-}
-__device__ __forceinline__ float4 clamp4(float4 v, int clamp) {
-  return make_float4(clamp1(v.x, clamp), clamp1(v.y, clamp), clamp1(v.z, clamp), clamp1(v.w, clamp));
-}
-
-// a = gamma / sqrt(var + eps), b = beta - a * mean into ab[0..C) and ab[C..2C): alignq_bnq_eval_fwd's statement (correctly rounded
-// fp32 sqrt and quotient, formed in double and rounded once more: with 53 >= 2 * 24 + 2 significand bits the second rounding cannot
-// change the result)
-__device__ __forceinline__ void ab_table(float* ab, int C, const SiteDev& s) {
-  for (int c = threadIdx.x; c < C; c += kThreads) {
-    const float sd = (float)sqrt((double)__fadd_rn(s.var[c], s.eps));
-    const float a = (float)((double)(s.gamma ? s.gamma[c] : 1.0f) / (double)sd);
-    ab[c] = a;
-    ab[C + c] = __fsub_rn(s.beta ? s.beta[c] : 0.0f, __fmul_rn(a, s.mean[c]));
-  }
-}
-
-// q(a z + b) of one channel quad.  FORMULA: 0 = ALIGNQ_FORMULA_ADMM, 1 = ALIGNQ_FORMULA_CDF, 2 = no quantiser (k == 32).
-template <int FORMULA, bool BOUNDED>
-__device__ __forceinline__ float4 site_q(const float4 v, const float* ab, int C, int cq, int k, const Levels& nlev, float r,
-                                         const NerfTab tab) {
-  const float4 a4 = *reinterpret_cast<const float4*>(ab + 4 * cq);
-  const float4 b4 = *reinterpret_cast<const float4*>(ab + C + 4 * cq);
-  float4 o;
-  o.x = __fadd_rn(__fmul_rn(a4.x, v.x), b4.x);
-  o.y = __fadd_rn(__fmul_rn(a4.y, v.y), b4.y);
-  o.z = __fadd_rn(__fmul_rn(a4.z, v.z), b4.z);
-  o.w = __fadd_rn(__fmul_rn(a4.w, v.w), b4.w);
-  if constexpr (FORMULA != 2) {
-    float t, bin;
-    o.x = act_quant1<FORMULA, BOUNDED>(o.x, k, nlev, r, &t, &bin, tab);
-    o.y = act_quant1<FORMULA, BOUNDED>(o.y, k, nlev, r, &t, &bin, tab);
-    o.z = act_quant1<FORMULA, BOUNDED>(o.z, k, nlev, r, &t, &bin, tab);
-    o.w = act_quant1<FORMULA, BOUNDED>(o.w, k, nlev, r, &t, &bin, tab);
-  }
-  return o;
 }
 
 __device__ __forceinline__ float4 add4(const float4 a, const float4 b) {
@@ -110,8 +63,8 @@ __global__ __launch_bounds__(kThreads) void site_eval_kernel(const SiteDev A, co
   __shared__ __attribute__((aligned(16))) float tab_lds[ALIGNQ_NERF_LDS_FLOATS];
   extern __shared__ __attribute__((aligned(16))) float ab_s[];      // [2][C] of A, then [2][C] of B: sized by the launch
   if (kQuant) nerf_tab_load(tab_lds);
-  ab_table(ab_s, C, A);
-  if (kTwin) ab_table(ab_s + 2 * C, C, B);
+  ab_table<kThreads>(ab_s, C, A);
+  if (kTwin) ab_table<kThreads>(ab_s + 2 * C, C, B);
   __syncthreads();
   const NerfTab tab = nerf_tab(tab_lds);
   const bool bounded_r = fabsf(r) <= 8.0f;
@@ -188,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void dwconv_site_eval_kernel(const float*
   extern __shared__ __attribute__((aligned(16))) float ab_s[];      // [2][C]
   const int C = CQ * 4;
   if (FORMULA != 2) nerf_tab_load(tab_lds);
-  ab_table(ab_s, C, A);
+  ab_table<kThreads>(ab_s, C, A);
   __syncthreads();
   const NerfTab tab = nerf_tab(tab_lds);
   const Levels nlev = make_levels(A.k, fabsf(r) <= 8.0f);

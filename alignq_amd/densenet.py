@@ -14,6 +14,11 @@ Every weight and activation quantiser runs on this repository's kernels.  With u
 dense layers (CIN = 24, 36, ..., 444 -> 12: multiples of 4, not of 8) run on csrc/k3conv_kernels.hip (include/alignq_k3conv.h) and
 the two transitions on csrc/pointwise_kernels.hip; the 3 -> 24 stem, batch-norm, the pools and the linear layer go to MIOpen /
 rocBLAS through PyTorch-ROCm.  The sites run as the composition; training is eager iterations (alignq_amd.optimizer.SGD).
+
+Evaluation (eval_step.EvalStep) with use_hip_convs(model, dense_eval=True): DenseNet._forward_eval keeps ONE buffer per dense block;
+a dense layer is one alignq_dense_layer_eval_fwd launch (include/alignq_dense.h: the site applied while the convolution stages its
+input, the 12 output channels written right behind the input), nothing is concatenated, and a transition's pool writes into the
+next block's buffer.
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import cdf_alignment as _cdf
-from . import ops, paths
+from . import fused, ops, paths
 
 
 def conv2d_Q3_fn(w_bit, stage):
@@ -77,6 +82,8 @@ class Transition(nn.Module):
 
 
 class DenseNet(nn.Module):
+    fuse_dense_eval = False           # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+
     def __init__(self, wbit, abit, stage, depth=40, block=DenseBasicBlock, dropRate=0, num_classes=10, growthRate=12,
                  compressionRate=2, filters=None, indexes=None):
         super().__init__()
@@ -126,6 +133,8 @@ class DenseNet(nn.Module):
         return transition(self.stage, self.wbit, self.abit, inplanes, outplanes, filters, index)
 
     def forward(self, x):
+        if self.fuse_dense_eval and fused.eval_active():
+            return self._forward_eval(x)
         x = self.dense1(self.conv1(x))
         x = self.dense2(self.trans1(x))
         x = self.dense3(self.trans2(x))
@@ -133,14 +142,69 @@ class DenseNet(nn.Module):
         return self.fc(x.reshape(x.size(0), -1))
 
 
+    # ---- evaluation without concatenations (inside fused.eval_scope: eval_step.EvalStep) ----
+    def _forward_eval(self, x):
+        """forward() with one buffer per dense block (168 / 312 / 456 channels at depth 40): the block's input is copied into its
+        first channels once, every dense layer is one launch in place (fused.dense_layer_eval), a transition is its site on the full
+        buffer (fused.site_eval_any), the 1x1 convolution and the pool into the next block's buffer (fused.avgpool2_into), the head its
+        site, the pool and the linear layer.  Whatever has no kernel runs the composition of forward().  Dropout is inactive in
+        evaluation."""
+        x = self._dense_eval(self.dense1, self.conv1(x), None)
+        x = self._dense_eval(self.dense2, *self._transition_eval(self.trans1, x, self.dense2))
+        x = self._dense_eval(self.dense3, *self._transition_eval(self.trans2, x, self.dense3))
+        y = fused.site_eval_any(self.bn, self.act_q0, x, fused.CLAMP_RELU)
+        if y is None:
+            y = self.relu(self.act_q0(self.bn(x)))
+        x = self.avgpool(y)
+        return self.fc(x.reshape(x.size(0), -1))
+
+    @staticmethod
+    def _block_buffer(dense, B, H, W, device):
+        c_end = dense[0].bn1.num_features + sum(layer.conv1.out_channels for layer in dense)
+        return torch.empty((B, c_end, H, W), dtype=torch.float32, device=device, memory_format=torch.channels_last)
+
+    def _dense_eval(self, dense, x, buf):
+        """One dense block.  x: its input, or None when `buf` already holds it in its first channels."""
+        if len(dense) == 0 or self.training:
+            return dense(x)
+        cin = dense[0].bn1.num_features
+        if buf is None:
+            if not (fused._nhwc_f32(x) and x.shape[1] == cin):
+                return dense(x)
+            buf = self._block_buffer(dense, x.shape[0], x.shape[2], x.shape[3], x.device)
+            buf[:, :cin].copy_(x)
+        for i, layer in enumerate(dense):
+            if fused.dense_layer_eval(layer.conv1, layer.bn1, layer.act_q0, buf, cin) is None:
+                # the composition for the rest of the block, on the channels filled so far
+                return dense[i:](buf[:, :cin].contiguous(memory_format=torch.channels_last))
+            cin += layer.conv1.out_channels
+        return buf
+
+    def _transition_eval(self, trans, x, dense):
+        """(x, None) = the transition's output, or (None, buf) with the output in the first channels of the next block's buffer"""
+        y = fused.site_eval_any(trans.bn1, trans.act_q0, x, fused.CLAMP_RELU)
+        if y is None:
+            y = trans.relu(trans.act_q0(trans.bn1(x)))
+        z = trans.conv1(y)
+        if len(dense) and fused._nhwc_f32(z) and z.shape[1] == dense[0].bn1.num_features and z.shape[2] >= 2 and z.shape[3] >= 2:
+            buf = self._block_buffer(dense, z.shape[0], z.shape[2] // 2, z.shape[3] // 2, z.device)
+            if fused.avgpool2_into(z, buf) is not None:
+                return None, buf
+        return F.avg_pool2d(z, 2), None
+
+
 def densenet_40_quant(bitW, abitW, stage, pretrained=False, **kwargs):
     return DenseNet(wbit=bitW, abit=abitW, stage=stage, depth=40, block=DenseBasicBlock, compressionRate=1, **kwargs)
 
 
-def use_hip_convs(model):
+def use_hip_convs(model, dense_eval=False):
     """Channels-last parameters plus `use_qconv`, `use_qconv_pw` (the transitions) and `use_qconv_k3` (the dense layers): with
     channels-last inputs every dense layer then runs on alignq_k3conv_* and both transitions on alignq_pwconv_*; the concatenations keep
-    the layout, so no dense layer falls back to MIOpen.  Values, parameter names and state_dict are unchanged."""
+    the layout, so no dense layer falls back to MIOpen.  Values, parameter names and state_dict are unchanged.
+    dense_eval=True also sets `fuse_dense_eval`: inside eval_step.EvalStep the model then runs DenseNet._forward_eval (one launch per
+    dense layer, no concatenation); every other forward is unchanged."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_pw=True, use_qconv_k3=True)
+    if dense_eval:
+        paths.apply(model, fuse_dense_eval=True)
     return model

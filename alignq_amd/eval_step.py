@@ -17,7 +17,10 @@ reads it); ties are ranked as include/alignq.h states for alignq_eval_metrics.  
 (channels-last fp32, C a power of two in [4, 2048], a quantiser of 1..16 bits or none): any other site runs today's `model.eval()`
 composition, which at an ADMM site does form the Grams and the loss and does store ADMM.D.  mobilenet.MobileNetV2 folds its sites
 itself inside the step (fused.site_eval_any / site_eval_twin / dw_site_eval, include/alignq_mobile.h: any C % 4 == 0 in [4, 2048],
-ReLU6, the stride-1 block tail, the depthwise convolution with its site as the epilogue).
+ReLU6, the stride-1 block tail, the depthwise convolution with its site as the epilogue).  densenet.DenseNet with
+`fuse_dense_eval` (densenet.use_hip_convs(model, dense_eval=True)) runs DenseNet._forward_eval inside the step: one buffer per dense
+block, every dense layer one launch with its site inside the 3x3 convolution (fused.dense_layer_eval, include/alignq_dense.h), no
+concatenation; without the flag a DenseNet runs today's composition.
 
     ev = EvalStep(skeleton, weights=export.PackedModel.load(path))     # evaluate from packed k-bit codes (export.py): begin()
                                                                        # unpacks them; the model's fp32 filters are never read"""
@@ -33,7 +36,7 @@ from .train_step import _CapturedStep
 
 class EvalStep(_CapturedStep):
     """model: resnet.PreActResNet (tree "admm" or "cdf"), resnet_office.DANN (class logits at alpha = 0), resnet_office.DSAN
-    (s_pred) or mobilenet.MobileNetV2.  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
+    (s_pred), mobilenet.MobileNetV2 or densenet.DenseNet.  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
     without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
     end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
 
@@ -65,8 +68,9 @@ class EvalStep(_CapturedStep):
     # ------------------------------------------------------------------------------------------- lifecycle
     def _pack_filters(self):
         """Whether begin() also leaves the filters' integer bins for the GEMM convolutions: the Office models, and any model whose
-        Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)) - once per evaluation, not per batch and layer"""
-        return self.qconv and (self._office or any(c.use_qconv_pw for c in self.all_convs))
+        Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)) or `use_qconv_k3` (densenet.use_hip_convs: the
+        dense layers' launches read the parked bins) - once per evaluation, not per batch and layer"""
+        return self.qconv and (self._office or any(c.use_qconv_pw or getattr(c, "use_qconv_k3", False) for c in self.all_convs))
 
     def _quantize_weights(self):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second

@@ -1244,6 +1244,63 @@ def dw_site_eval(conv, bn, act, x, clamp):
     return y
 
 
+# DenseNet's evaluation without concatenations (include/alignq_dense.h, csrc/dense_eval_kernels.hip): one buffer per dense block,
+# every layer one launch that reads the buffer's first `cin` channels and writes its own right behind them; the transition's pool
+# writes into the next block's buffer.  Each returns None where its kernel does not apply; the caller then composes the modules.
+def dense_layer_eval(conv, bn, act, buf, cin):
+    """buf[:, cin:cin + C_out] = conv(relu(act(bn.eval()(buf[:, :cin])))) for a 3x3 / stride 1 / padding 1 Conv2d_Q by one
+    alignq_dense_layer_eval_fwd launch, in place: the quantised prefix is never written and nothing is concatenated.  Returns buf.
+    None where `use_qconv` / `use_qconv_k3` are off, the filter is not parked with its bins (EvalStep.begin parks it), buf is not a
+    channels-last fp32 CUDA tensor with room for the output, the batch-norm is not an eval-mode one with running statistics over
+    `cin` channels, the quantiser has no folded form or the shape is outside alignq_k3conv_fwd's set."""
+    from . import config
+    if not (getattr(conv, "use_qconv", False) and getattr(conv, "use_qconv_k3", False) and _nhwc_f32(buf)):
+        return None
+    q = conv.quantize_fn
+    w, w_bit = conv.weight, int(getattr(q, "w_bit", 32))
+    parked = q.parked
+    if not (1 <= w_bit <= 8) or parked is None or parked.weight is not w or parked.bins is None:
+        return None
+    if conv.bias is not None or conv.groups != 1 or tuple(conv.kernel_size) != (3, 3):
+        return None
+    if tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1):
+        return None
+    if not w.is_contiguous(memory_format=torch.channels_last):          # (the bins lie as the filter does: [C_out][3][3][C_in])
+        return None
+    B, C_end, H, W = buf.shape
+    cin, cout = int(cin), int(conv.out_channels)
+    if conv.in_channels != cin or cin + cout > C_end or C_end % 4 or B * H * W * C_end > 2 ** 31 - 1:
+        return None
+    lib = L.load()
+    if lib.alignq_k3conv_supported(B, H, W, cin, cout) != 1:
+        return None
+    kf = _eval_site(bn, act, cin)
+    if kf is None:
+        return None
+    site = L.DenseSite(L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var), float(bn.eps), int(kf[0]),
+                       int(CLAMP_RELU))
+    x = buf.data_ptr()
+    rc = lib.alignq_dense_layer_eval_fwd(x, C_end, x + 4 * cin, C_end, ctypes.byref(site), L.ptr(parked.bins[0]), B, H, W, cin, cout,
+                                         w_bit, float(config.args.act_range), int(kf[1]), L.stream_ptr())
+    L.check(rc, "alignq_dense_layer_eval_fwd")
+    return buf
+
+
+def avgpool2_into(z, buf):
+    """buf[:, :C] = F.avg_pool2d(z, 2) by one alignq_avgpool2_nhwc_fwd launch (the window summed row-major, then * 0.25); z (B, C, H, W)
+    and buf (B, C_end >= C, H // 2, W // 2) channels-last fp32 CUDA tensors.  Returns buf, or None where the kernel does not apply."""
+    if not (_nhwc_f32(z) and _nhwc_f32(buf)):
+        return None
+    B, C, H, W = z.shape
+    C_end = buf.shape[1]
+    if tuple(buf.shape) != (B, C_end, H // 2, W // 2) or H < 2 or W < 2 or C % 4 or C_end % 4 or not (4 <= C <= min(C_end, 2048)):
+        return None
+    if z.numel() > 2 ** 31 - 1 or buf.numel() > 2 ** 31 - 1:
+        return None
+    L.check(L.load().alignq_avgpool2_nhwc_fwd(L.ptr(z), L.ptr(buf), C_end, B, H, W, C, L.stream_ptr()), "alignq_avgpool2_nhwc_fwd")
+    return buf
+
+
 def bn_only(bn, z, groups=1):
     """bn(z): the folded-family kernels when the tensor is channels-last fp32 in training mode, else the module itself
     (groups > 1: applied to the batch slices one after the other, as the reference's successive passes do)."""

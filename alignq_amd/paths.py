@@ -1,12 +1,13 @@
 """The kernel-path flags of a model, set in one place.
 
 A module class that reads a flag declares it as a class attribute holding its off value (quantization.Conv2d_Q, resnet.PreActBlock_conv_Q
-/ PreActResNet, resnet_office.Bottleneck / ResNet, densenet.Conv2d_Q3; the table is in DESIGN.md).  `apply` assigns a flag on every module of a model whose
+/ PreActResNet, resnet_office.Bottleneck / ResNet, densenet.Conv2d_Q3 / DenseNet; the table is in DESIGN.md).  `apply` assigns a flag on every module of a model whose
 class declares it and on no other; `restore` puts back what `apply` found.  The flags stay plain attributes: `m.use_qconv = False` on
 one module works as before."""
 from __future__ import annotations
 
-FLAGS = ("use_qconv", "use_qconv_pw", "emit_bn_stats", "fuse_bn", "fuse_relu", "pack_bins", "_wq_stage", "use_qconv_k3")
+FLAGS = ("use_qconv", "use_qconv_pw", "emit_bn_stats", "fuse_bn", "fuse_relu", "pack_bins", "_wq_stage", "use_qconv_k3",
+         "fuse_dense_eval")
 _ABSENT = object()
 
 
