@@ -3,7 +3,7 @@
 //
 //   alignq_dense_layer_eval_fwd : one dense layer, bn1 -> act_q0 -> ReLU -> 3x3 Conv2d_Q, as ONE launch.  The kernel is
 //                               k3_gemm_kernel<TN, false> of k3conv_kernels.hip (same tile, same staging, same MFMA order, same
-//                               epilogue) with two changes: pixels are addressed through a pitch on both sides, so that the layer
+//                               epilogue, the primitives of exact_mma.h) with two changes: pixels are addressed through a pitch on both sides, so that the layer
 //                               reads the first CIN channels of its block's buffer and writes its COUT channels right behind them;
 //                               and the site (eval_site_body.h: the statement mobile_eval_kernels.hip uses) is applied to a float4 of
 //                               the halo tile between its load and its split into three bf16 terms.  What is not loaded - the padding,
@@ -18,21 +18,16 @@
 
 #include "../../include/alignq.h"
 #include "../../include/alignq_dense.h"
-#include "../../include/alignq_k3conv.h"
 #include "alignq_math.h"
 #include "eval_site_body.h"
-#include "store_forms.h"
+#include "exact_conv_host.h"
+#include "exact_mma.h"
 
 using namespace alignq;
 using namespace alignq_evalsite;
+using namespace alignq_xmma;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 // the geometry of k3conv_kernels.hip's forward
 constexpr int BK = 32;                 // channels per chunk (one MFMA k step)
@@ -42,41 +37,6 @@ constexpr int HS = TS + 2, HP = HS * HS;          // with its halo: 10 x 10
 constexpr int kMaxTileBlocks = 2048;   // grid cap over spatial tiles; the rest by grid stride
 constexpr int kMinC = 4, kMaxC = 512;
 constexpr int kPoolMaxC = 2048, kPoolMaxGrid = 2048, kPoolThreads = 256;
-constexpr int64_t kWtMinBytes = (int64_t)1 << 20, kWtMaxBytes = (int64_t)64 << 20;      // write-through window (store_forms.h)
-
-__device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// exact three-way split of four floats, v == hi + mid + lo: split3 of k3conv_kernels.hip, the same bits
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_bf16x2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
-__device__ __forceinline__ f32x2 bf16x2_as_f32(unsigned b) {
-  return (f32x2){__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)};
-}
-__device__ __forceinline__ void split3(const f32x4 v, s16x4& h, s16x4& m, s16x4& l) {
-  const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const unsigned ha = cvt_bf16x2(a), hb = cvt_bf16x2(b);
-  const f32x2 ra = a - bf16x2_as_f32(ha), rb = b - bf16x2_as_f32(hb);
-  const unsigned ma = cvt_bf16x2(ra), mb = cvt_bf16x2(rb);
-  const f32x2 sa = ra - bf16x2_as_f32(ma), sb = rb - bf16x2_as_f32(mb);
-  h = __builtin_bit_cast(s16x4, (u32x2){ha, hb});
-  m = __builtin_bit_cast(s16x4, (u32x2){ma, mb});
-  l = __builtin_bit_cast(s16x4, (u32x2){cvt_bf16x2(sa), cvt_bf16x2(sb)});
-}
-
-// Workgroups that share operand rows on one XCD (qgemm_kernels.hip): bijective for any n.
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  const int q = n >> 3, r = n & 7, x = id & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
-}
-
-__device__ __forceinline__ void st_out(float* p, const f32x4 v, const int wt) {
-  if (wt) alignq_store::st16<alignq_store::kConvOut>(p, make_float4(v[0], v[1], v[2], v[3]));
-  else *reinterpret_cast<f32x4*>(p) = v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // y[b][h][w][n] = (1 / nlev) * sum_{t = (ty, tx)} sum_k s(x[b][h + ty - 1][w + tx - 1][k]) * w[n][t][k],  s = the site of channel k;
@@ -242,21 +202,10 @@ __global__ __launch_bounds__(kPoolThreads) void avgpool2_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------ host ----------------------
-inline bool mis16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 inline bool bad_k(int k) { return !((k >= 1 && k <= 16) || k == 32); }
 inline bool bad_formula(int f) { return f != ALIGNQ_FORMULA_ADMM && f != ALIGNQ_FORMULA_CDF; }
 inline bool bad_clamp(int c) { return c != ALIGNQ_CLAMP_NONE && c != ALIGNQ_CLAMP_RELU && c != ALIGNQ_CLAMP_RELU6; }
 inline bool bad_pitch(int ld, int width) { return (ld & 3) != 0 || ld < width; }
-
-// B * H * W * ld <= 2^31 - 1, without overflow
-inline bool fits31(int B, int H, int W, int ld) {
-  const int64_t lim = INT32_MAX;
-  int64_t m = (int64_t)B * H;
-  if (m > lim) return false;
-  m *= W;
-  if (m > lim) return false;
-  return m * ld <= lim;
-}
 
 inline bool layer_shape_ok(int B, int H, int W, int CIN, int COUT, int ldx, int ldy) {
   if (CIN < kMinC || CIN > kMaxC || (CIN & 3) || COUT < kMinC || COUT > kMaxC || (COUT & 3) || B < 1 || H < 1 || W < 1) return false;
@@ -281,7 +230,7 @@ extern "C" {
 
 int alignq_dense_layer_eval_fwd(const float* x, int ldx, float* y, int ldy, const alignq_dense_site* site, const void* w_bins, int B,
                                 int H, int W, int CIN, int COUT, int w_bit, float act_range, int formula, void* stream) {
-  if (!x || !y || !w_bins || !site || !site->running_mean || !site->running_var || mis16(x) || mis16(y) || mis16(w_bins))
+  if (!x || !y || !w_bins || !site || !site->running_mean || !site->running_var || !aligned16(x) || !aligned16(y) || !aligned16(w_bins))
     return ALIGNQ_EINVAL;
   if (w_bit < 1 || w_bit > 8 || bad_k(site->k) || bad_formula(formula) || bad_clamp(site->clamp)) return ALIGNQ_EINVAL;
   if (bad_pitch(ldx, CIN) || bad_pitch(ldy, COUT)) return ALIGNQ_EINVAL;
@@ -297,24 +246,22 @@ int alignq_dense_layer_eval_fwd(const float* x, int ldx, float* y, int ldy, cons
   p.s_blocks = p.s_tiles < kMaxTileBlocks ? p.s_tiles : kMaxTileBlocks;
   p.nlev = (float)((1 << w_bit) - 1);
   p.r = act_range;
-  const int64_t bytes = (int64_t)B * H * W * COUT * (int64_t)sizeof(float);
-  p.wt = bytes >= kWtMinBytes && bytes <= kWtMaxBytes;
-  const int form = alignq_k3conv_form(ALIGNQ_K3_FWD, 1, 1, 1, CIN, COUT);          // a function of COUT alone
-  const int bn = form == ALIGNQ_K3_FORM_N64 ? 64 : (form == ALIGNQ_K3_FORM_N32 ? 32 : 16);
+  p.wt = write_through((int64_t)B * H * W * COUT * (int64_t)sizeof(float));
+  const int bn = n_tile_width(COUT);
   p.n_tiles = (COUT + bn - 1) / bn;
   const bool bounded = make_levels(site->k, fabsf(act_range) <= 8.0f).yn != 0.0f;
   const int variant = site->k == 32 ? 4 : (formula == ALIGNQ_FORMULA_CDF ? 2 : 0) + (bounded ? 1 : 0);
   const dim3 grid(p.s_blocks * p.n_tiles);
   hipStream_t st = (hipStream_t)stream;
-  if (form == ALIGNQ_K3_FORM_N64) launch_layer<4>(p, variant, grid, st);
-  else if (form == ALIGNQ_K3_FORM_N32) launch_layer<2>(p, variant, grid, st);
+  if (bn == 64) launch_layer<4>(p, variant, grid, st);
+  else if (bn == 32) launch_layer<2>(p, variant, grid, st);
   else launch_layer<1>(p, variant, grid, st);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
 
 int alignq_avgpool2_nhwc_fwd(const float* x, float* y, int ldy, int B, int H, int W, int C, void* stream) {
-  if (!x || !y || mis16(x) || mis16(y) || bad_pitch(ldy, C)) return ALIGNQ_EINVAL;
+  if (!x || !y || !aligned16(x) || !aligned16(y) || bad_pitch(ldy, C)) return ALIGNQ_EINVAL;
   if (C < 4 || C > kPoolMaxC || (C & 3) || B < 1 || H < 2 || W < 2) return ALIGNQ_EUNSUPPORTED;
   if (!fits31(B, H, W, C) || !fits31(B, H / 2, W / 2, ldy)) return ALIGNQ_EUNSUPPORTED;
   const int Ho = H / 2, Wo = W / 2, CQ = C / 4;

@@ -2,7 +2,7 @@
 // quantization.py, F.conv2d(input, weight_q, ...)) at any channel count that is a multiple of 4: DenseNet-40's dense layers,
 // CIN = 24, 36, ..., 444 -> COUT = 12.  Forward, data gradient and filter gradient with the arithmetic of pointwise_kernels.hip:
 // the filter's integer bins as bf16, the fp32 operand in three exact bf16 terms, v_mfma_f32_16x16x32_bf16, fp32 accumulation in an
-// order the shape fixes, one division.  include/alignq_k3conv.h states the contract.  The geometry:
+// order the shape fixes, one division (the primitives: exact_mma.h; the launchers' shared rules: exact_conv_host.h).  include/alignq_k3conv.h states the contract.  The geometry:
 //   forward / data gradient  one workgroup = 256 threads = 4 waves = an 8 x 8 pixel tile of ONE image x 16, 32 or 64 output channels.
 //           Per 32-deep channel chunk the tile WITH ITS HALO (10 x 10 pixels) is staged in LDS once, already split into the three
 //           term images; the nine taps read it at shifted rows, so an element is split once, not nine times.  Halo pixels outside
@@ -19,16 +19,13 @@
 
 #include "../../include/alignq.h"
 #include "../../include/alignq_k3conv.h"
-#include "store_forms.h"
+#include "exact_conv_host.h"
+#include "exact_mma.h"
 #include "wgrad_reduce_body.h"
 
-namespace {
+using namespace alignq_xmma;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+namespace {
 
 constexpr int BK = 32;                 // channels per chunk (one MFMA k step)
 constexpr int LDX = BK + 8;            // halfwords per LDS row: 80 B rows, 16 lanes' ds_read_b128 on 16 distinct 16-byte slots
@@ -36,45 +33,6 @@ constexpr int TS = 8;                  // forward / data gradient: the spatial t
 constexpr int HS = TS + 2, HP = HS * HS;          // with its halo: 10 x 10
 constexpr int kMaxTileBlocks = 2048;   // grid cap over spatial tiles; the rest by grid stride
 constexpr int kMinC = 4, kMaxC = 512;
-constexpr int64_t kWtMinBytes = (int64_t)1 << 20, kWtMaxBytes = (int64_t)64 << 20;      // write-through window (store_forms.h)
-
-__device__ __forceinline__ s16x4 tr_read(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ s16x8 join8(s16x4 a, s16x4 b) { return (s16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-__device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// exact three-way split of four floats, v == hi + mid + lo: split3 of qgemm_kernels.hip, the same bits
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_bf16x2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
-__device__ __forceinline__ f32x2 bf16x2_as_f32(unsigned b) {
-  return (f32x2){__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)};
-}
-__device__ __forceinline__ void split3(const f32x4 v, s16x4& h, s16x4& m, s16x4& l) {
-  const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const unsigned ha = cvt_bf16x2(a), hb = cvt_bf16x2(b);
-  const f32x2 ra = a - bf16x2_as_f32(ha), rb = b - bf16x2_as_f32(hb);
-  const unsigned ma = cvt_bf16x2(ra), mb = cvt_bf16x2(rb);
-  const f32x2 sa = ra - bf16x2_as_f32(ma), sb = rb - bf16x2_as_f32(mb);
-  h = __builtin_bit_cast(s16x4, (u32x2){ha, hb});
-  m = __builtin_bit_cast(s16x4, (u32x2){ma, mb});
-  l = __builtin_bit_cast(s16x4, (u32x2){cvt_bf16x2(sa), cvt_bf16x2(sb)});
-}
-
-// Workgroups that share operand rows on one XCD (qgemm_kernels.hip): bijective for any n.
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  const int q = n >> 3, r = n & 7, x = id & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
-}
-
-__device__ __forceinline__ void st_out(float* p, const f32x4 v, const int wt) {
-  if (wt) alignq_store::st16<alignq_store::kConvOut>(p, make_float4(v[0], v[1], v[2], v[3]));
-  else *reinterpret_cast<f32x4*>(p) = v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Forward and data gradient:  out[b][h][w][n] = (1 / nlev) * sum_{t = (ty, tx)} sum_k a[b][h + ty - 1][w + tx - 1][k] * Wb(n, t, k)
@@ -361,24 +319,14 @@ __global__ __launch_bounds__(kRedThreads) void k3_slab_reduce_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline bool shape_ok(int B, int H, int W, int CIN, int COUT) {
   if (CIN < kMinC || CIN > kMaxC || (CIN & 3) || COUT < kMinC || COUT > kMaxC || (COUT & 3) || B < 1 || H < 1 || W < 1) return false;
-  const int64_t lim = INT32_MAX;
-  int64_t m = (int64_t)B * H;
-  if (m > lim) return false;
-  m *= W;
-  if (m > lim) return false;
-  return m * (CIN > COUT ? CIN : COUT) <= lim;
+  return fits31(B, H, W, CIN > COUT ? CIN : COUT);
 }
 
-// the widest tile that pads N by no more than rounding it up to 16 does (pointwise_kernels.hip)
 inline int gemm_form(int N) {
-  const int r16 = (N + 15) / 16 * 16;
-  if ((N + 63) / 64 * 64 == r16) return ALIGNQ_K3_FORM_N64;
-  if ((N + 31) / 32 * 32 == r16) return ALIGNQ_K3_FORM_N32;
-  return ALIGNQ_K3_FORM_N16;
+  const int bn = n_tile_width(N);
+  return bn == 64 ? ALIGNQ_K3_FORM_N64 : (bn == 32 ? ALIGNQ_K3_FORM_N32 : ALIGNQ_K3_FORM_N16);
 }
 inline int wgrad_form(int CIN, int COUT) { return CIN >= COUT ? ALIGNQ_K3_FORM_W64X16 : ALIGNQ_K3_FORM_W16X64; }
 
@@ -391,14 +339,12 @@ int launch_gemm(const float* a, const void* w, float* out, int B, int H, int W, 
   p.s_tiles = B * p.th * p.tw;                       // <= B * H * W
   p.s_blocks = p.s_tiles < kMaxTileBlocks ? p.s_tiles : kMaxTileBlocks;
   p.nlev = (float)((1 << w_bit) - 1);
-  const int64_t bytes = (int64_t)B * H * W * N * (int64_t)sizeof(float);
-  p.wt = bytes >= kWtMinBytes && bytes <= kWtMaxBytes;
-  const int form = gemm_form(N);
-  const int bn = form == ALIGNQ_K3_FORM_N64 ? 64 : (form == ALIGNQ_K3_FORM_N32 ? 32 : 16);
+  p.wt = write_through((int64_t)B * H * W * N * (int64_t)sizeof(float));
+  const int bn = n_tile_width(N);
   p.n_tiles = (N + bn - 1) / bn;
   const dim3 grid(p.s_blocks * p.n_tiles), blk(256);
-  if (form == ALIGNQ_K3_FORM_N64) hipLaunchKernelGGL((k3_gemm_kernel<4, WTR>), grid, blk, 0, st, p);
-  else if (form == ALIGNQ_K3_FORM_N32) hipLaunchKernelGGL((k3_gemm_kernel<2, WTR>), grid, blk, 0, st, p);
+  if (bn == 64) hipLaunchKernelGGL((k3_gemm_kernel<4, WTR>), grid, blk, 0, st, p);
+  else if (bn == 32) hipLaunchKernelGGL((k3_gemm_kernel<2, WTR>), grid, blk, 0, st, p);
   else hipLaunchKernelGGL((k3_gemm_kernel<1, WTR>), grid, blk, 0, st, p);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

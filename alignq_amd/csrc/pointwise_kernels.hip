@@ -2,7 +2,8 @@
 // F.conv2d(input, weight_q, ...)) at MobileNet-V2's widths: channel counts that are multiples of 8, not of 64 (16 -> 96, 96 -> 24,
 // 24 -> 144, 144 -> 32, 576 -> 160 ...).  Forward, data gradient and filter gradient with the arithmetic of qgemm_kernels.hip's
 // general-operand form (MODE 0): the filter's integer bins as bf16, the fp32 operand in three exact bf16 terms,
-// v_mfma_f32_16x16x32_bf16, fp32 accumulation in an order the shape fixes, one division.  include/alignq_pointwise.h states the
+// v_mfma_f32_16x16x32_bf16, fp32 accumulation in an order the shape fixes, one division (the primitives both files run: exact_mma.h;
+// the launchers' shared rules: exact_conv_host.h).  include/alignq_pointwise.h states the
 // contract.  What differs from qgemm_kernel is the geometry:
 //   K edge  the contraction length is a multiple of 8: the tail of the last 64-deep k step is zero-filled in LDS on both operands
 //           (a 32-deep half step that holds nothing but zeros is skipped: a choice the shape makes);
@@ -17,61 +18,19 @@
 
 #include "../../include/alignq.h"
 #include "../../include/alignq_pointwise.h"
-#include "store_forms.h"
+#include "exact_conv_host.h"
+#include "exact_mma.h"
 #include "wgrad_reduce_body.h"
 
-namespace {
+using namespace alignq_xmma;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+namespace {
 
 constexpr int BK = 64;                 // k per step (two MFMA k-substeps)
 constexpr int BM = 64;                 // pixels per workgroup tile
 constexpr int LDX = BK + 16;           // halfwords per LDS row: 160 B rows keep ds_read_b128 conflict-free (qgemm_kernels.hip)
 constexpr int kMaxRowBlocks = 2048;    // grid cap over row tiles; the rest by grid stride
 constexpr int kMinC = 8, kMaxC = 2048;
-constexpr int64_t kWtMinBytes = (int64_t)1 << 20, kWtMaxBytes = (int64_t)64 << 20;      // write-through window (store_forms.h)
-
-__device__ __forceinline__ s16x4 tr_read(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ s16x8 join8(s16x4 a, s16x4 b) { return (s16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-__device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// exact three-way split of four floats, v == hi + mid + lo: split3 of qgemm_kernels.hip, the same bits
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_bf16x2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
-__device__ __forceinline__ f32x2 bf16x2_as_f32(unsigned b) {
-  return (f32x2){__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)};
-}
-__device__ __forceinline__ void split3(const f32x4 v, s16x4& h, s16x4& m, s16x4& l) {
-  const f32x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-  const unsigned ha = cvt_bf16x2(a), hb = cvt_bf16x2(b);
-  const f32x2 ra = a - bf16x2_as_f32(ha), rb = b - bf16x2_as_f32(hb);
-  const unsigned ma = cvt_bf16x2(ra), mb = cvt_bf16x2(rb);
-  const f32x2 sa = ra - bf16x2_as_f32(ma), sb = rb - bf16x2_as_f32(mb);
-  h = __builtin_bit_cast(s16x4, (u32x2){ha, hb});
-  m = __builtin_bit_cast(s16x4, (u32x2){ma, mb});
-  l = __builtin_bit_cast(s16x4, (u32x2){cvt_bf16x2(sa), cvt_bf16x2(sb)});
-}
-
-// Workgroups that share operand rows on one XCD (qgemm_kernels.hip): bijective for any n.
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  const int q = n >> 3, r = n & 7, x = id & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
-}
-
-__device__ __forceinline__ void st_out(float* p, const f32x4 v, const int wt) {
-  if (wt) alignq_store::st16<alignq_store::kConvOut>(p, make_float4(v[0], v[1], v[2], v[3]));
-  else *reinterpret_cast<f32x4*>(p) = v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Forward and data gradient:  out[m][n] = (1 / nlev) * sum_k a[m][k] * Wb(n, k)
@@ -328,19 +287,14 @@ __global__ __launch_bounds__(kRedThreads) void pw_slab_reduce_kernel(const float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline bool shape_ok(int64_t M, int CIN, int COUT) {
   if (CIN < kMinC || CIN > kMaxC || (CIN & 7) || COUT < kMinC || COUT > kMaxC || (COUT & 7) || M < 1) return false;
   return M * (CIN > COUT ? CIN : COUT) <= (int64_t)INT32_MAX;
 }
 
-// the widest tile that pads N by no more than rounding it up to 16 does
 inline int gemm_form(int N) {
-  const int r16 = (N + 15) / 16 * 16;
-  if ((N + 63) / 64 * 64 == r16) return ALIGNQ_PW_FORM_N64;
-  if ((N + 31) / 32 * 32 == r16) return ALIGNQ_PW_FORM_N32;
-  return ALIGNQ_PW_FORM_N16;
+  const int bn = n_tile_width(N);
+  return bn == 64 ? ALIGNQ_PW_FORM_N64 : (bn == 32 ? ALIGNQ_PW_FORM_N32 : ALIGNQ_PW_FORM_N16);
 }
 inline int wgrad_form(int CIN, int COUT) { return (CIN <= 32 ? 0 : 1) + (COUT <= 32 ? 0 : 2); }
 
@@ -352,14 +306,12 @@ int launch_gemm(const float* a, const void* w, float* out, int64_t M, int K, int
   p.m_tiles = (int)((M + BM - 1) / BM);
   p.m_blocks = p.m_tiles < kMaxRowBlocks ? p.m_tiles : kMaxRowBlocks;
   p.nlev = (float)((1 << w_bit) - 1);
-  const int64_t bytes = M * N * (int64_t)sizeof(float);
-  p.wt = bytes >= kWtMinBytes && bytes <= kWtMaxBytes;
-  const int form = gemm_form(N);
-  const int bn = form == ALIGNQ_PW_FORM_N64 ? 64 : (form == ALIGNQ_PW_FORM_N32 ? 32 : 16);
+  p.wt = write_through(M * N * (int64_t)sizeof(float));
+  const int bn = n_tile_width(N);
   p.n_tiles = (N + bn - 1) / bn;
   const dim3 grid(p.m_blocks * p.n_tiles), blk(256);
-  if (form == ALIGNQ_PW_FORM_N64) hipLaunchKernelGGL((pw_gemm_kernel<4, WTR>), grid, blk, 0, st, p);
-  else if (form == ALIGNQ_PW_FORM_N32) hipLaunchKernelGGL((pw_gemm_kernel<2, WTR>), grid, blk, 0, st, p);
+  if (bn == 64) hipLaunchKernelGGL((pw_gemm_kernel<4, WTR>), grid, blk, 0, st, p);
+  else if (bn == 32) hipLaunchKernelGGL((pw_gemm_kernel<2, WTR>), grid, blk, 0, st, p);
   else hipLaunchKernelGGL((pw_gemm_kernel<1, WTR>), grid, blk, 0, st, p);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
