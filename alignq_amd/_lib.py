@@ -82,34 +82,19 @@ def load():
         fn.restype, fn.argtypes = res, args
     if lib.alignq_abi_version() != ABI_VERSION:
         raise AlignQLibraryError("libalignq_hip.so ABI version mismatch; rebuild")
-    for name, (res, args) in MOBILE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_mobile.h): it was built before "
-                                     "csrc/mobile_eval_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
-        fn.restype, fn.argtypes = res, args
-    for name, (res, args) in POINTWISE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_pointwise.h): it was built before "
-                                     "csrc/pointwise_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
-        fn.restype, fn.argtypes = res, args
-    for name, (res, args) in K3CONV_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_k3conv.h): it was built before "
-                                     "csrc/k3conv_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
-        fn.restype, fn.argtypes = res, args
-    for name, (res, args) in DENSE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/alignq_dense.h): it was built before "
-                                     "csrc/dense_eval_kernels.hip existed; rebuild it with `make -C alignq_amd/csrc`") from None
-        fn.restype, fn.argtypes = res, args
+    # the extension tables, in the order they were added (read from the module's globals now: a test models an older library by
+    # emptying one)
+    for table, header, source in (("MOBILE_SIGNATURES", "alignq_mobile.h", "mobile_eval_kernels.hip"),
+                                  ("POINTWISE_SIGNATURES", "alignq_pointwise.h", "pointwise_kernels.hip"),
+                                  ("K3CONV_SIGNATURES", "alignq_k3conv.h", "k3conv_kernels.hip"),
+                                  ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip")):
+        for name, (res, args) in globals()[table].items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise AlignQLibraryError(f"{SO_PATH} does not export {name} (include/{header}): it was built before "
+                                         f"csrc/{source} existed; rebuild it with `make -C alignq_amd/csrc`") from None
+            fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
 

@@ -29,24 +29,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import cdf_alignment as _cdf
-from . import fused, ops, paths
+from . import fused, paths
 
 
 def conv2d_Q3_fn(w_bit, stage):
-    """Conv2d_Q of the CDF namespace plus one opt-in branch: the 3x3 / stride 1 / padding 1 convolutions at channel counts that are
-    multiples of 4 on alignq_k3conv_*.  The flag is declared HERE, not on Conv2d_Q: no other model's modules carry it."""
+    """Conv2d_Q of the CDF namespace plus one opt-in flag: with it the 3x3 / stride 1 / padding 1 convolutions at channel counts that
+    are multiples of 4 run on alignq_k3conv_*, ahead of every other family (ops.conv2d_q reads the flag).  The flag is declared HERE,
+    not on Conv2d_Q: no other model's modules carry it."""
     base = _cdf.conv2d_Q_fn(w_bit=w_bit, stage=stage)
 
     class Conv2d_Q3(base):
         use_qconv_k3 = False          # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
-
-        def _conv(self, input, weight_q):
-            if self.use_qconv and self.use_qconv_k3 and getattr(input, "_alignq_bins", None) is None:
-                if ops.qconv_k3_supported(input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
-                                          self.quantize_fn.w_bit):
-                    rec = self.quantize_fn.filter_of(weight_q)
-                    return ops.QConvK3Fn.apply(input, weight_q, self.quantize_fn.w_bit, rec.bins)
-            return super()._conv(input, weight_q)
 
     return Conv2d_Q3
 

@@ -1253,27 +1253,22 @@ def dense_layer_eval(conv, bn, act, buf, cin):
     None where `use_qconv` / `use_qconv_k3` are off, the filter is not parked with its bins (EvalStep.begin parks it), buf is not a
     channels-last fp32 CUDA tensor with room for the output, the batch-norm is not an eval-mode one with running statistics over
     `cin` channels, the quantiser has no folded form or the shape is outside alignq_k3conv_fwd's set."""
-    from . import config
+    from . import config, ops
     if not (getattr(conv, "use_qconv", False) and getattr(conv, "use_qconv_k3", False) and _nhwc_f32(buf)):
         return None
     q = conv.quantize_fn
     w, w_bit = conv.weight, int(getattr(q, "w_bit", 32))
     parked = q.parked
-    if not (1 <= w_bit <= 8) or parked is None or parked.weight is not w or parked.bins is None:
-        return None
-    if conv.bias is not None or conv.groups != 1 or tuple(conv.kernel_size) != (3, 3):
-        return None
-    if tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1):
-        return None
-    if not w.is_contiguous(memory_format=torch.channels_last):          # (the bins lie as the filter does: [C_out][3][3][C_in])
+    if parked is None or parked.weight is not w or parked.bins is None:
         return None
     B, C_end, H, W = buf.shape
     cin, cout = int(cin), int(conv.out_channels)
-    if conv.in_channels != cin or cin + cout > C_end or C_end % 4 or B * H * W * C_end > 2 ** 31 - 1:
+    if cin + cout > C_end or C_end % 4 or B * H * W * C_end > 2 ** 31 - 1:
+        return None
+    # what the k3 family takes of the buffer's first cin channels (the bins lie as the channels-last filter does: [C_out][3][3][C_in])
+    if not ops.qconv_k3_shape_supported((B, cin, H, W), w, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, w_bit):
         return None
     lib = L.load()
-    if lib.alignq_k3conv_supported(B, H, W, cin, cout) != 1:
-        return None
     kf = _eval_site(bn, act, cin)
     if kf is None:
         return None

@@ -557,14 +557,32 @@ def site_res_supported(x, residual) -> bool:
 
 
 # ------------------------------------------------------------------------------------------------ R9 (Conv2d_Q's conv)
+# What the Conv2d_Q predicates share.  Every `*_supported` below reads: these, then what is particular to its family; conv2d_q (at the
+# end of this file) asks them in order.
+def _quantised_conv(dilation, groups, bias, w_bit) -> bool:
+    """The module's side of every family but the depthwise one: no bias, one group, dilation 1, a filter from a 1..8-bit quantiser"""
+    return bias is None and groups == 1 and 1 <= w_bit <= 8 and tuple(dilation) == (1, 1)
+
+
+def _cuda_f32(t) -> bool:
+    return t.is_cuda and t.dtype == torch.float32
+
+
+def _nhwc_input(x, strict=False) -> bool:
+    """A CUDA fp32 4-D channels-last tensor.  strict: and not plain-contiguous as well (a tensor is both when C == 1 or H == W == 1)"""
+    return (_cuda_f32(x) and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+            and not (strict and x.is_contiguous()))
+
+
 def qconv3x3_shape_supported(shape, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """Shapes alignq_conv3x3_nhwc implements, for an input given by its SHAPE only (a packed handle, fused.packed_handle): 3x3 /
     stride 1 / padding 1, C_in == C_out in {16,32,64} at width 32 / 16 / 8 (the ResNet-20/56 body), a <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or len(shape) != 4:
+    if not _quantised_conv(dilation, groups, bias, w_bit) or len(shape) != 4:
         return False
-    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1):
+    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1):
         return False
     B, C, H, W = shape
+    # (w.is_cuda is not asked: the callers ask it of the input, or - conv2d_q's packed rung, whose handle has no data - of w themselves)
     if w.dtype != torch.float32 or tuple(w.shape) != (C, C, 3, 3) or (C, W) not in ((16, 32), (32, 16), (64, 8)):
         return False
     # tiles are 8 / 8 / 4-8 whole image rows
@@ -573,11 +591,9 @@ def qconv3x3_shape_supported(shape, w, stride, padding, dilation, groups, bias, 
 
 def qconv3x3_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """qconv3x3_shape_supported for a channels-last fp32 tensor.  Everything else stays on MIOpen."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
-        return False
-    if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
-        return False
-    return qconv3x3_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
+    # (strict layout: as found.  It is the form of fused._is_nhwc, which the channels-last batch-norm fold brought in a few commits
+    # before this family to tell its two layout branches apart; the four strict families - this one, gen, stem, depthwise - repeat it)
+    return _nhwc_input(x, strict=True) and qconv3x3_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
 
 
 def _call_img(name, n_front, imgs, *args):
@@ -721,18 +737,16 @@ class QConv3x3Fn(torch.autograd.Function):
 def qconv_gen_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """The transition convolutions alignq_conv_gen_nhwc_fwd implements: stride 2, 3x3 (padding 1) or 1x1 (padding 0),
     (C_in, C_out, W_in) in {(16, 32, 32), (32, 64, 16)}, channels-last fp32, <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or tuple(stride) != (2, 2) or tuple(dilation) != (1, 1):
+    if not _quantised_conv(dilation, groups, bias, w_bit) or tuple(stride) != (2, 2):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32):
+    # (strict layout, and w.is_cuda not asked beside the input's: as found)
+    if not (_nhwc_input(x, strict=True) and w.dtype == torch.float32):
         return False
     B, CIN, H, W = x.shape
     COUT, ks = w.shape[0], w.shape[2]
     if tuple(w.shape) != (COUT, CIN, ks, ks) or (ks, tuple(padding)) not in ((3, (1, 1)), (1, (0, 0))):
         return False
-    cl = torch.channels_last
-    if not (x.is_contiguous(memory_format=cl) and not x.is_contiguous()):
-        return False
-    if not (w.is_contiguous(memory_format=cl) or (ks == 1 and w.is_contiguous())):
+    if not (w.is_contiguous(memory_format=torch.channels_last) or (ks == 1 and w.is_contiguous())):
         return False
     return L.load().alignq_conv_gen_bn_parts(B, H, W, CIN, COUT, ks, 2) > 0
 
@@ -888,9 +902,7 @@ def qconv_gemm_shape_supported(shape, w, stride, padding, dilation, groups, bias
     """The Conv2d_Q convolutions alignq_qconv_* take (the ResNet-50 / Office-31 shapes of BASELINE config 5), for an input given by its
     SHAPE only (a packed handle, fused.packed_handle: the values live in int16 level indices laid out channels-last): C_in and C_out
     multiples of 64, 1x1 (padding 0) or 3x3 (padding 1), stride 1 or 2, <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or tuple(dilation) != (1, 1) or len(shape) != 4:
-        return False
-    if not (w.dtype == torch.float32 and w.is_cuda):
+    if not (_quantised_conv(dilation, groups, bias, w_bit) and len(shape) == 4 and _cuda_f32(w)):
         return False
     B, CIN, H, W = shape
     COUT, ks = w.shape[0], w.shape[2]
@@ -905,9 +917,8 @@ def qconv_gemm_shape_supported(shape, w, stride, padding, dilation, groups, bias
 
 def qconv_gemm_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """qconv_gemm_shape_supported for a channels-last fp32 tensor."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    return qconv_gemm_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
+    # (plain channels-last, a 1 x 1 map included: as found)
+    return _nhwc_input(x) and qconv_gemm_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
 
 
 def level_count(t):
@@ -998,16 +1009,16 @@ class QConvGemmFn(torch.autograd.Function):
 def qconv_stem7_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """The Office ResNet-50's stem (dann_office/model/resnet.py:193-195: Conv2d_Q(3, 64, kernel_size=7, stride=2, padding=3)) as
     alignq_qconv_stem7_fwd takes it: channels-last fp32 image that needs no gradient, <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or x.requires_grad:
+    if not _quantised_conv(dilation, groups, bias, w_bit) or x.requires_grad:
         return False
-    if tuple(stride) != (2, 2) or tuple(padding) != (3, 3) or tuple(dilation) != (1, 1):
+    if tuple(stride) != (2, 2) or tuple(padding) != (3, 3):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32 and w.is_cuda):
+    # (plain channels-last, as the GEMM family whose file holds the kernel: as found)
+    if not (_nhwc_input(x) and _cuda_f32(w)):
         return False
     B, C, H, W = x.shape
-    cl = torch.channels_last
-    return (C == 3 and tuple(w.shape) == (64, 3, 7, 7) and H >= 8 and W >= 8 and x.is_contiguous(memory_format=cl)
-            and w.is_contiguous(memory_format=cl) and bool(L.load().alignq_qconv_stem7_bn_parts(B, H, W, 1)))
+    return (C == 3 and tuple(w.shape) == (64, 3, 7, 7) and H >= 8 and W >= 8 and w.is_contiguous(memory_format=torch.channels_last)
+            and bool(L.load().alignq_qconv_stem7_bn_parts(B, H, W, 1)))
 
 
 class QConvStem7Fn(torch.autograd.Function):
@@ -1058,16 +1069,15 @@ class QConvStem7Fn(torch.autograd.Function):
 def qconv_stem_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
     """The stem convolution alignq_conv_stem_nhwc_fwd implements: 3 -> 16 channels, 3x3 / stride 1 / padding 1, width 32,
     channels-last fp32 input that needs no gradient, <= 8-bit quantised filter."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8) or x.requires_grad:
+    if not _quantised_conv(dilation, groups, bias, w_bit) or x.requires_grad:
         return False
-    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1):
+    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32):
+    # (strict layout, and w.is_cuda not asked beside the input's: as found)
+    if not (_nhwc_input(x, strict=True) and w.dtype == torch.float32):
         return False
     B, C, H, W = x.shape
-    cl = torch.channels_last
-    return (C == 3 and tuple(w.shape) == (16, 3, 3, 3) and W == 32 and H % 4 == 0 and x.is_contiguous(memory_format=cl)
-            and not x.is_contiguous() and w.is_contiguous(memory_format=cl))
+    return C == 3 and tuple(w.shape) == (16, 3, 3, 3) and W == 32 and H % 4 == 0 and w.is_contiguous(memory_format=torch.channels_last)
 
 
 class QConvStemFn(torch.autograd.Function):
@@ -1117,14 +1127,14 @@ def qconv_dw_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> 
     """The depthwise convolutions alignq_dwconv3x3_nhwc_fwd implements (MobileNet-V2's `conv2`): groups == C_in == C_out, filter
     (C, 1, 3, 3), padding 1, dilation 1, stride 1 or 2, no bias, channels-last fp32 input, C % 4 == 0.  Any w_bit: the kernels read
     the fp32 W_q, whatever produced it (also the w_bit == 32 pass-through)."""
+    # (not _quantised_conv: one group per channel, and the kernels read the fp32 W_q of any w_bit)
     if bias is not None or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1) or tuple(stride) not in ((1, 1), (2, 2)):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32):
+    # (strict layout: as found)
+    if not (_nhwc_input(x, strict=True) and _cuda_f32(w)):
         return False
     B, C, H, W = x.shape
     if groups != C or tuple(w.shape) != (C, 1, 3, 3) or not w.is_contiguous():
-        return False
-    if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
         return False
     return L.load().alignq_dwconv3x3_supported(B, H, W, C, stride[0]) == 1
 
@@ -1170,18 +1180,48 @@ def qconv_pw_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> 
     """The pointwise convolutions alignq_pwconv_* take (include/alignq_pointwise.h; MobileNet-V2's conv1 / conv3 / shortcuts): a
     (C_out, C_in, 1, 1) filter, stride 1, padding 0, dilation 1, groups 1, no bias, <= 8-bit quantised filter, channels-last fp32
     input, C_in and C_out multiples of 8 in [8, 2048]."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8):
+    if not _quantised_conv(dilation, groups, bias, w_bit) or tuple(stride) != (1, 1) or tuple(padding) != (0, 0):
         return False
-    if tuple(stride) != (1, 1) or tuple(padding) != (0, 0) or tuple(dilation) != (1, 1):
-        return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and tuple(w.shape[1:]) == (x.shape[1], 1, 1)):
+    # (plain channels-last, a 1 x 1 map included: as found)
+    if not (_nhwc_input(x) and _cuda_f32(w) and w.dim() == 4 and tuple(w.shape[1:]) == (x.shape[1], 1, 1)):
         return False
     if not (w.is_contiguous() or w.is_contiguous(memory_format=torch.channels_last)):
         return False
     B, CIN, H, W = x.shape
     return L.load().alignq_pwconv_supported(B * H * W, CIN, w.shape[0]) == 1
+
+
+def _bins_conv_fwd(ctx, prefix, geom, n_elem, x, w, w_bit, bins):
+    """The forward QConvPwFn and QConvK3Fn share: `prefix`_fwd on the filter's bf16 bins, stride 1, the output of the input's height and
+    width.  prefix: the family's entry points (`prefix`_fwd / _dgrad / _wgrad / _wgrad_ws_bytes); geom: the geometry arguments those
+    take between the pointers and w_bit; n_elem: the filter gradient's element count.  The backward is _bins_conv_bwd."""
+    if bins is None:
+        bins = pack_filter_bins([w], w_bit)[0]
+    B, _, H, W = x.shape
+    y = torch.empty((B, w.shape[0], H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
+    L.check(getattr(L.load(), prefix + "_fwd")(L.ptr(x), L.ptr(bins[0]), L.ptr(y), *geom, int(w_bit), L.stream_ptr()), prefix + "_fwd")
+    ctx.save_for_backward(x, w, bins[0])
+    ctx.cfg = (prefix, geom, n_elem, int(w_bit))
+    return y
+
+
+def _bins_conv_bwd(ctx, gy):
+    x, w, wb = ctx.saved_tensors
+    prefix, geom, n_elem, w_bit = ctx.cfg
+    lib = L.load()
+    cl = torch.channels_last
+    if not gy.is_contiguous(memory_format=cl):
+        gy = gy.contiguous(memory_format=cl)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty(tuple(x.shape), dtype=torch.float32, device=w.device, memory_format=cl)
+        L.check(getattr(lib, prefix + "_dgrad")(L.ptr(gy), L.ptr(wb), L.ptr(dx), *geom, w_bit, L.stream_ptr()), prefix + "_dgrad")
+    if ctx.needs_input_grad[1]:
+        dw = torch.empty_like(w)
+        ws = _ws(getattr(lib, prefix + "_wgrad_ws_bytes")(*geom), w.device)
+        _filter_grad(ws, dw, n_elem, lambda dwp, nsp: L.check(getattr(lib, prefix + "_wgrad")(
+            L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), *geom, nsp, L.stream_ptr()), prefix + "_wgrad"))
+    return dx, dw, None, None
 
 
 class QConvPwFn(torch.autograd.Function):
@@ -1194,53 +1234,29 @@ class QConvPwFn(torch.autograd.Function):
     def forward(ctx, x, w, w_bit, bins=None):
         B, CIN, H, W = x.shape
         COUT = w.shape[0]
-        if bins is None:
-            bins = pack_filter_bins([w], w_bit)[0]
-        y = torch.empty((B, COUT, H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
-        L.check(L.load().alignq_pwconv_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B * H * W, CIN, COUT, int(w_bit), L.stream_ptr()),
-                "alignq_pwconv_fwd")
-        ctx.save_for_backward(x, w, bins[0])
-        ctx.w_bit = int(w_bit)
-        return y
+        return _bins_conv_fwd(ctx, "alignq_pwconv", (B * H * W, CIN, COUT), COUT * CIN, x, w, w_bit, bins)
 
-    @staticmethod
-    def backward(ctx, gy):
-        x, w, wb = ctx.saved_tensors
-        B, CIN, H, W = x.shape
-        COUT, M = w.shape[0], B * H * W
-        lib = L.load()
-        cl = torch.channels_last
-        if not gy.is_contiguous(memory_format=cl):
-            gy = gy.contiguous(memory_format=cl)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((B, CIN, H, W), dtype=torch.float32, device=w.device, memory_format=cl)
-            L.check(lib.alignq_pwconv_dgrad(L.ptr(gy), L.ptr(wb), L.ptr(dx), M, CIN, COUT, ctx.w_bit, L.stream_ptr()),
-                    "alignq_pwconv_dgrad")
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            ws = _ws(lib.alignq_pwconv_wgrad_ws_bytes(M, CIN, COUT), w.device)
-            _filter_grad(ws, dw, COUT * CIN, lambda dwp, nsp: L.check(lib.alignq_pwconv_wgrad(
-                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), M, CIN, COUT, nsp, L.stream_ptr()), "alignq_pwconv_wgrad"))
-        return dx, dw, None, None
+    backward = staticmethod(_bins_conv_bwd)
+
+
+def qconv_k3_shape_supported(shape, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The 3x3 convolutions alignq_k3conv_* take (include/alignq_k3conv.h; DenseNet-40's dense layers), for an input given by its SHAPE
+    only (fused.dense_layer_eval: the first channels of a wider buffer): a (C_out, C_in, 3, 3) channels-last CUDA fp32 filter, stride 1,
+    padding 1, dilation 1, groups 1, no bias, <= 8-bit quantised filter, C_in and C_out multiples of 4 in [4, 512]."""
+    if not _quantised_conv(dilation, groups, bias, w_bit) or len(shape) != 4:
+        return False
+    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1):
+        return False
+    B, CIN, H, W = shape
+    if not (_cuda_f32(w) and w.dim() == 4 and tuple(w.shape[1:]) == (CIN, 3, 3) and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return L.load().alignq_k3conv_supported(B, H, W, CIN, w.shape[0]) == 1
 
 
 def qconv_k3_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
-    """The 3x3 convolutions alignq_k3conv_* take (include/alignq_k3conv.h; DenseNet-40's dense layers): a (C_out, C_in, 3, 3)
-    channels-last filter, stride 1, padding 1, dilation 1, groups 1, no bias, <= 8-bit quantised filter, channels-last fp32 input,
-    C_in and C_out multiples of 4 in [4, 512]."""
-    if bias is not None or groups != 1 or not (1 <= w_bit <= 8):
-        return False
-    if tuple(stride) != (1, 1) or tuple(padding) != (1, 1) or tuple(dilation) != (1, 1):
-        return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and tuple(w.shape[1:]) == (x.shape[1], 3, 3)):
-        return False
-    if not w.is_contiguous(memory_format=torch.channels_last):
-        return False
-    B, CIN, H, W = x.shape
-    return L.load().alignq_k3conv_supported(B, H, W, CIN, w.shape[0]) == 1
+    """qconv_k3_shape_supported for a channels-last fp32 tensor."""
+    # (plain channels-last, a 1 x 1 map included: as found)
+    return _nhwc_input(x) and qconv_k3_shape_supported(tuple(x.shape), w, stride, padding, dilation, groups, bias, w_bit)
 
 
 class QConvK3Fn(torch.autograd.Function):
@@ -1253,32 +1269,78 @@ class QConvK3Fn(torch.autograd.Function):
     def forward(ctx, x, w, w_bit, bins=None):
         B, CIN, H, W = x.shape
         COUT = w.shape[0]
-        if bins is None:
-            bins = pack_filter_bins([w], w_bit)[0]
-        y = torch.empty((B, COUT, H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
-        L.check(L.load().alignq_k3conv_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B, H, W, CIN, COUT, int(w_bit), L.stream_ptr()),
-                "alignq_k3conv_fwd")
-        ctx.save_for_backward(x, w, bins[0])
-        ctx.w_bit = int(w_bit)
-        return y
+        return _bins_conv_fwd(ctx, "alignq_k3conv", (B, H, W, CIN, COUT), COUT * 9 * CIN, x, w, w_bit, bins)
 
-    @staticmethod
-    def backward(ctx, gy):
-        x, w, wb = ctx.saved_tensors
-        B, CIN, H, W = x.shape
-        COUT = w.shape[0]
-        lib = L.load()
-        cl = torch.channels_last
-        if not gy.is_contiguous(memory_format=cl):
-            gy = gy.contiguous(memory_format=cl)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((B, CIN, H, W), dtype=torch.float32, device=w.device, memory_format=cl)
-            L.check(lib.alignq_k3conv_dgrad(L.ptr(gy), L.ptr(wb), L.ptr(dx), B, H, W, CIN, COUT, ctx.w_bit, L.stream_ptr()),
-                    "alignq_k3conv_dgrad")
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            ws = _ws(lib.alignq_k3conv_wgrad_ws_bytes(B, H, W, CIN, COUT), w.device)
-            _filter_grad(ws, dw, COUT * 9 * CIN, lambda dwp, nsp: L.check(lib.alignq_k3conv_wgrad(
-                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), B, H, W, CIN, COUT, nsp, L.stream_ptr()), "alignq_k3conv_wgrad"))
-        return dx, dw, None, None
+    backward = staticmethod(_bins_conv_bwd)
+
+
+# ------------------------------------------------------------------------------------------------ which family a convolution gets
+def _gemm_node(conv, x, w, w_bit, bins, xbins=None):
+    """The GEMM family with or without the batch-norm statistics of its output (emit_bn_stats: the batch-norm behind this convolution
+    takes them from the epilogue, fused.conv_partials, per batch slice of fused.conv_groups())"""
+    if conv.emit_bn_stats:
+        return QConvGemmFn.apply_with_stats(x, w, w_bit, conv.stride[0], level_count(x), fused.conv_groups(), bins, xbins)
+    return QConvGemmFn.apply(x, w, w_bit, conv.stride[0], level_count(x), 1, bins, xbins)
+
+
+def conv2d_q(conv, x, w, tap=False):
+    """The kernel family of one Conv2d_Q convolution: conv(x) with the quantised filter `w` (what conv.quantize_fn returned) on the
+    first family below that takes it, or - for a tensor x - None where torch's convolution is to run.  This is the whole decision
+    (Conv2d_Q._conv and forward_with_shortcut only call it); the order is behaviour, because several shapes are taken by more than one
+    family.  No family is asked unless conv.use_qconv is set.  The one thing done here whatever the flag: a packed handle that no
+    family takes is materialised, and torch's convolution of its fp32 tensor is returned, so a handle never comes back as None.
+
+    x a packed handle (fused.packed_handle: its values are the int8 / int16 level indices riding on it):
+      1. QConv3x3Fn     the ResNet-20/56 body reads the indices
+      2. QConvGemmFn    the ResNet-50 shapes read int16 indices that carry the level tag
+      any other handle is materialised, and its fp32 tensor goes down the rungs from 4
+    x a tensor:
+      3. QConvK3Fn      3x3 at multiples of 4, only where the module declares and sets use_qconv_k3 (densenet.Conv2d_Q3)
+      4. QConv3x3Fn     the ResNet-20/56 body
+      5. QConvGenFn     the stride-2 transition convolutions
+      6. QConvStemFn    3 -> 16
+      7. QConvStem7Fn   the Office stem, 7x7 / stride 2, 3 -> 64
+      8. QConvGemmFn    the ResNet-50 shapes: channel counts that are multiples of 64
+      9. QConvDwFn      MobileNet-V2's depthwise 3x3
+      10. QConvPwFn     1x1 at multiples of 8, only with use_qconv_pw (the multiples of 64 stay on 8)
+    tap (forward_with_shortcut: the result is (y, alias of x), the alias an output of the same node): rungs 4 and 5 alone, and only
+    for an x that needs a gradient; on None the caller returns (its plain convolution, x)."""
+    use, w_bit = conv.use_qconv, conv.quantize_fn.w_bit
+    if tap and not (use and x.requires_grad):
+        return None
+    rec = conv.quantize_fn.filter_of(w) if use else None     # the bins / image the quantiser holds for this very tensor, if any
+    args = (w, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, w_bit)
+    packed = None if tap else getattr(x, "_alignq_bins", None)      # (with tap a handle is a tensor no rung takes)
+    if packed is not None:
+        bins, a_bit = packed
+        if use and w.is_cuda and qconv3x3_shape_supported(tuple(x.shape), *args):
+            return QConv3x3Fn.apply_with_stats(x, w, w_bit, False, bins, a_bit, rec.image)
+        if use and bins.dtype == torch.int16 and level_count(x) and qconv_gemm_shape_supported(tuple(x.shape), *args):
+            return _gemm_node(conv, x, w, w_bit, rec.bins, bins)
+        x = fused.materialize(x)
+    if use:
+        # (a materialised handle skips the k3 rung: as found - Conv2d_Q3 put it in front of the handling of handles, for tensors only)
+        if packed is None and not tap and getattr(conv, "use_qconv_k3", False) and qconv_k3_supported(x, *args):
+            return QConvK3Fn.apply(x, w, w_bit, rec.bins)
+        # (4 - 6 with the batch-norm statistics of the output as a by-product for fused.bn_site)
+        if qconv3x3_supported(x, *args):
+            return QConv3x3Fn.apply_with_stats(x, w, w_bit, tap, img=rec.image)
+        if qconv_gen_supported(x, *args):      # (tap in a transition block: the alias feeds the shortcut convolution)
+            return QConvGenFn.apply_with_stats(x, w, w_bit, conv.padding[0], tap, img=rec.image)
+        if tap:
+            return None
+        if qconv_stem_supported(x, *args):
+            return QConvStemFn.apply_with_stats(x, w, w_bit)
+        if qconv_stem7_supported(x, *args):
+            if conv.emit_bn_stats:
+                return QConvStem7Fn.apply_with_stats(x, w, w_bit, fused.conv_groups(), rec.bins)
+            return QConvStem7Fn.apply(x, w, w_bit, 1, rec.bins)
+        if qconv_gemm_supported(x, *args):
+            return _gemm_node(conv, x, w, w_bit, rec.bins)
+        if qconv_dw_supported(x, *args):
+            return QConvDwFn.apply(x, w, conv.stride[0])
+        if conv.use_qconv_pw and qconv_pw_supported(x, *args):
+            return QConvPwFn.apply(x, w, w_bit, rec.bins)
+    if packed is None:
+        return None
+    return torch.nn.functional.conv2d(x, w, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)

@@ -282,63 +282,9 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 return self._conv(input, self.quantize_fn(self.weight))
 
             def _conv(self, input, weight_q):
-                rec = self.quantize_fn.filter_of(weight_q)     # the bins / image the quantiser holds for this very tensor, if any
-                packed = getattr(input, "_alignq_bins", None)
-                if packed is not None:
-                    # N2: the input is a packed handle (fused.bn_site(pack=True)): its values are int8 / int16 level
-                    # indices; the 3x3 body convolution reads them directly, anything else gets the dequantised tensor
-                    bins, a_bit = packed
-                    if (self.use_qconv and weight_q.is_cuda
-                            and ops.qconv3x3_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
-                                                             self.groups, self.bias, self.quantize_fn.w_bit)):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, False, bins, a_bit,
-                                                               rec.image)
-                    if (self.use_qconv and bins.dtype == torch.int16 and ops.level_count(input)
-                            and ops.qconv_gemm_shape_supported(tuple(input.shape), weight_q, self.stride, self.padding, self.dilation,
-                                                               self.groups, self.bias, self.quantize_fn.w_bit)):
-                        # the ResNet-50 shapes: the GEMM kernels read the int16 indices directly (forward and filter gradient)
-                        fb = rec.bins
-                        if self.emit_bn_stats:
-                            from . import fused
-                            return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
-                                                                    ops.level_count(input), fused.conv_groups(), fb, bins)
-                        return ops.QConvGemmFn.apply(input, weight_q, self.quantize_fn.w_bit, self.stride[0], ops.level_count(input),
-                                                     1, fb, bins)
-                    from . import fused
-                    input = fused.materialize(input)
-                # opt-in: the convolutions on the matrix cores
-                # (with the batch-norm statistics of the output as a by-product for fused.bn_site)
-                if self.use_qconv:
-                    args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
-                            self.quantize_fn.w_bit)
-                    if ops.qconv3x3_supported(*args):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit,
-                                                               img=rec.image)
-                    if ops.qconv_gen_supported(*args):
-                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0],
-                                                               img=rec.image)
-                    if ops.qconv_stem_supported(*args):
-                        return ops.QConvStemFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit)
-                    if ops.qconv_stem7_supported(*args):     # the Office stem (7x7, stride 2, 3 -> 64 channels)
-                        bins = rec.bins
-                        if self.emit_bn_stats:
-                            from . import fused
-                            return ops.QConvStem7Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, fused.conv_groups(), bins)
-                        return ops.QConvStem7Fn.apply(input, weight_q, self.quantize_fn.w_bit, 1, bins)
-                    if ops.qconv_gemm_supported(*args):      # the ResNet-50 shapes: exact-product GEMMs (csrc/qgemm_kernels.hip)
-                        bins = rec.bins
-                        if self.emit_bn_stats:     # the batch-norm behind this convolution takes its statistics
-                            from . import fused                        # from the epilogue (fused.conv_partials)
-                            return ops.QConvGemmFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
-                                                                    ops.level_count(input), fused.conv_groups(), bins)
-                        return ops.QConvGemmFn.apply(input, weight_q, self.quantize_fn.w_bit, self.stride[0],
-                                                     ops.level_count(input), 1, bins)
-                    if ops.qconv_dw_supported(*args):        # MobileNet-V2's depthwise 3x3 (csrc/dwconv_kernels.hip)
-                        return ops.QConvDwFn.apply(input, weight_q, self.stride[0])
-                    # opt-in on top of use_qconv (mobilenet.use_hip_convs(model, pointwise=True)): the 1x1 convolutions whose channel
-                    # counts are multiples of 8 (csrc/pointwise_kernels.hip); the multiples of 64 stay on the branch above
-                    if self.use_qconv_pw and ops.qconv_pw_supported(*args):
-                        return ops.QConvPwFn.apply(input, weight_q, self.quantize_fn.w_bit, rec.bins)
+                out = ops.conv2d_q(self, input, weight_q)      # the family of this repository's kernels that takes it, if any
+                if out is not None:
+                    return out
                 return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
             def forward_with_shortcut(self, input):
@@ -347,16 +293,9 @@ def make_namespace(tree: str) -> types.SimpleNamespace:
                 kernels (and a gradient is needed) the alias is an output of the same autograd node, so the second gradient
                 is added inside the data-gradient kernel; otherwise plainly (forward(input), input)."""
                 weight_q = self.quantize_fn(self.weight)
-                if self.use_qconv and input.requires_grad:
-                    rec = self.quantize_fn.filter_of(weight_q)
-                    args = (input, weight_q, self.stride, self.padding, self.dilation, self.groups, self.bias,
-                            self.quantize_fn.w_bit)
-                    if ops.qconv3x3_supported(*args):
-                        return ops.QConv3x3Fn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, True,
-                                                               img=rec.image)
-                    if ops.qconv_gen_supported(*args):      # transition block: the alias feeds the shortcut convolution
-                        return ops.QConvGenFn.apply_with_stats(input, weight_q, self.quantize_fn.w_bit, self.padding[0], True,
-                                                               img=rec.image)
+                out = ops.conv2d_q(self, input, weight_q, tap=True)
+                if out is not None:
+                    return out
                 return self._conv(input, weight_q), input
 
         return Conv2d_Q

@@ -117,3 +117,31 @@ def test_the_positional_leftovers_are_gone():
         forward = getattr(cls, "forward", None)
         if forward is not None:          # (no placeholder parameters: nothing a caller has to skip by position)
             assert not [p for p in inspect.signature(forward).parameters if p.startswith("_")], name
+
+
+def test_every_family_refuses_cpu_tensors_before_it_reaches_for_the_library(monkeypatch):
+    """ops.conv2d_q with every kernel-path flag on and CPU tensors: each family's smallest accepted case (the base cases of
+    tests/golden/gen_goldens_conv_dispatch.py) gives torch's convolution bit for bit, from forward and from forward_with_shortcut, and
+    no predicate has loaded the library: their cheap checks refuse first"""
+    from alignq_amd import _lib, densenet
+    from alignq_amd import cdf_alignment_admm as admm
+    from tests.golden.gen_goldens_conv_dispatch import single_cases
+    monkeypatch.setattr(_lib, "_lib", None)
+    bases = [c for c in single_cases(Hg=16) if c["base"] is None and c["packed"] is None]
+    assert {c["name"] for c in bases} >= {"body", "gen3", "gen1", "stem", "stem7", "gemm1", "gemm3s2", "dw", "pw", "k3", "body64"}
+    cl = torch.channels_last
+    for c in bases:
+        cin, cout, ks, stride, pad, dil, groups, bias = c["conv"]
+        make = densenet.conv2d_Q3_fn if c["kind"] == "Q3" else admm.conv2d_Q_fn
+        conv = make(c["w_bit"], "second")(cin, cout, ks, stride, pad, dil, groups, bias).to(memory_format=cl)
+        for flag in ("use_qconv", "use_qconv_pw", "use_qconv_k3", "emit_bn_stats"):
+            if hasattr(type(conv), flag):
+                setattr(conv, flag, True)
+        x = torch.randn(c["x"], generator=torch.Generator().manual_seed(2)).contiguous(memory_format=cl).requires_grad_(c["x_grad"])
+        rec = _record(conv)
+        want = F.conv2d(x, rec.q, None, stride, pad, dil, groups)
+        conv.quantize_fn.park(rec, keep=True)
+        assert torch.equal(conv(x), want), c["name"]
+        y, alias = conv.forward_with_shortcut(x)
+        assert torch.equal(y, want) and alias is x, c["name"]
+    assert _lib._lib is None
