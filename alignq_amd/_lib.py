@@ -40,8 +40,13 @@ K3CONV_SIGNATURES, _K3CONV_STRUCTS, _K3CONV_CONSTANTS = _header.read(os.path.joi
 K3_FWD, K3_DGRAD, K3_WGRAD = (_K3CONV_CONSTANTS[n] for n in ("ALIGNQ_K3_FWD", "ALIGNQ_K3_DGRAD", "ALIGNQ_K3_WGRAD"))
 
 # DENSE_SIGNATURES: the entry points of include/alignq_dense.h (DenseNet's evaluation without concatenations: a dense layer's site
-# inside its 3x3 convolution, the transition's pool written at a pitch), a fifth table, bound last
+# inside its 3x3 convolution, the transition's pool written at a pitch), a fifth table, bound after the four above
 DENSE_SIGNATURES, _DENSE_STRUCTS, _DENSE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_dense.h"))
+
+# K5CONV_SIGNATURES: the entry points of include/alignq_k5conv.h (the 5x5 / stride 1 / padding 0 Conv2d_Q convolutions with a bias:
+# the digit-domain DANN's two layers), a sixth table, bound last
+K5CONV_SIGNATURES, _K5CONV_STRUCTS, _K5CONV_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k5conv.h"))
+K5_FWD, K5_DGRAD, K5_WGRAD = (_K5CONV_CONSTANTS[n] for n in ("ALIGNQ_K5_FWD", "ALIGNQ_K5_DGRAD", "ALIGNQ_K5_WGRAD"))
 
 
 class SiteBnArgs(ctypes.Structure):
@@ -87,7 +92,8 @@ def load():
     for table, header, source in (("MOBILE_SIGNATURES", "alignq_mobile.h", "mobile_eval_kernels.hip"),
                                   ("POINTWISE_SIGNATURES", "alignq_pointwise.h", "pointwise_kernels.hip"),
                                   ("K3CONV_SIGNATURES", "alignq_k3conv.h", "k3conv_kernels.hip"),
-                                  ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip")):
+                                  ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip"),
+                                  ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

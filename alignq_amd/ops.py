@@ -1274,6 +1274,69 @@ class QConvK3Fn(torch.autograd.Function):
     backward = staticmethod(_bins_conv_bwd)
 
 
+def qconv_k5_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The 5x5 convolutions alignq_k5conv_* take (include/alignq_k5conv.h; the digit-domain DANN's two layers): a (C_out, C_in, 5, 5)
+    channels-last CUDA fp32 filter, stride 1, padding 0, dilation 1, groups 1, <= 8-bit quantised filter, a channels-last fp32 input of
+    at least 5 x 5, C_out a multiple of 4 in [4, 512], C_in likewise (body form) or 3 (image form: no data gradient, so refused for an
+    input that needs one)."""
+    # (not _quantised_conv: this family takes a bias - a CUDA fp32 vector of C_out - or none)
+    if groups != 1 or not 1 <= w_bit <= 8 or tuple(dilation) != (1, 1) or tuple(stride) != (1, 1) or tuple(padding) != (0, 0):
+        return False
+    if not (_nhwc_input(x) and _cuda_f32(w) and w.dim() == 4 and tuple(w.shape[1:]) == (x.shape[1], 5, 5)
+            and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if bias is not None and not (_cuda_f32(bias) and tuple(bias.shape) == (w.shape[0],) and bias.is_contiguous()):
+        return False
+    B, CIN, H, W = x.shape
+    lib = L.load()
+    if x.requires_grad and lib.alignq_k5conv_supported(L.K5_DGRAD, B, H, W, CIN, w.shape[0]) != 1:
+        return False
+    return all(lib.alignq_k5conv_supported(op, B, H, W, CIN, w.shape[0]) == 1 for op in (L.K5_FWD, L.K5_WGRAD))
+
+
+class QConvK5Fn(torch.autograd.Function):
+    """F.conv2d(input, weight_q, bias, 1, 0) of Conv2d_Q.forward for a 5x5 filter, on alignq_k5conv_fwd / _dgrad / _wgrad
+    (csrc/k5conv_kernels.hip): exact products of the filter's integer bins and three bf16 terms of the fp32 operand, the bias added in
+    the epilogue.  bins: as QConvK3Fn's.  The bias gradient is gy summed over batch and pixels (torch); the filter gradient's slab
+    reduction is deferred to fused.DeferredWgrads when such a context is active.  (Its own forward and backward, not _bins_conv_*: a
+    bias pointer among the arguments, a third gradient, and an output smaller than the input.)"""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, w_bit, bins=None):
+        if bins is None:
+            bins = pack_filter_bins([w], w_bit)[0]
+        B, CIN, H, W = x.shape
+        COUT = w.shape[0]
+        y = torch.empty((B, COUT, H - 4, W - 4), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
+        L.check(L.load().alignq_k5conv_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(bias), L.ptr(y), B, H, W, CIN, COUT, int(w_bit),
+                                           L.stream_ptr()), "alignq_k5conv_fwd")
+        ctx.save_for_backward(x, w, bins[0])
+        ctx.w_bit = int(w_bit)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, wb = ctx.saved_tensors
+        lib = L.load()
+        cl = torch.channels_last
+        if not gy.is_contiguous(memory_format=cl):
+            gy = gy.contiguous(memory_format=cl)
+        B, CIN, H, W = x.shape
+        geom = (B, H, W, CIN, w.shape[0])
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(tuple(x.shape), dtype=torch.float32, device=w.device, memory_format=cl)
+            L.check(lib.alignq_k5conv_dgrad(L.ptr(gy), L.ptr(wb), L.ptr(dx), *geom, ctx.w_bit, L.stream_ptr()), "alignq_k5conv_dgrad")
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(w)
+            ws = _ws(lib.alignq_k5conv_wgrad_ws_bytes(*geom), w.device)
+            _filter_grad(ws, dw, w.numel(), lambda dwp, nsp: L.check(lib.alignq_k5conv_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), *geom, nsp, L.stream_ptr()), "alignq_k5conv_wgrad"))
+        if ctx.needs_input_grad[2]:
+            db = gy.sum((0, 2, 3))
+        return dx, dw, db, None, None
+
+
 # ------------------------------------------------------------------------------------------------ which family a convolution gets
 def _gemm_node(conv, x, w, w_bit, bins, xbins=None):
     """The GEMM family with or without the batch-norm statistics of its output (emit_bn_stats: the batch-norm behind this convolution
@@ -1296,6 +1359,8 @@ def conv2d_q(conv, x, w, tap=False):
       any other handle is materialised, and its fp32 tensor goes down the rungs from 4
     x a tensor:
       3. QConvK3Fn      3x3 at multiples of 4, only where the module declares and sets use_qconv_k3 (densenet.Conv2d_Q3)
+      3a. QConvK5Fn     5x5 / padding 0 with or without a bias, 3 or a multiple of 4 input channels, only where the module declares
+                        and sets use_qconv_k5 (digit.Conv2d_Q5); the one family that takes a bias
       4. QConv3x3Fn     the ResNet-20/56 body
       5. QConvGenFn     the stride-2 transition convolutions
       6. QConvStemFn    3 -> 16
@@ -1322,6 +1387,8 @@ def conv2d_q(conv, x, w, tap=False):
         # (a materialised handle skips the k3 rung: as found - Conv2d_Q3 put it in front of the handling of handles, for tensors only)
         if packed is None and not tap and getattr(conv, "use_qconv_k3", False) and qconv_k3_supported(x, *args):
             return QConvK3Fn.apply(x, w, w_bit, rec.bins)
+        if packed is None and not tap and getattr(conv, "use_qconv_k5", False) and qconv_k5_supported(x, *args):
+            return QConvK5Fn.apply(x, w, conv.bias, w_bit, rec.bins)
         # (4 - 6 with the batch-norm statistics of the output as a by-product for fused.bn_site)
         if qconv3x3_supported(x, *args):
             return QConv3x3Fn.apply_with_stats(x, w, w_bit, tap, img=rec.image)

@@ -4,7 +4,7 @@
  *
  * Why a fifth header: alignq.h is the core C ABI with a fixed set of entry points and ALIGNQ_ABI_VERSION; alignq_mobile.h,
  * alignq_pointwise.h and alignq_k3conv.h are fixed sets too.  This extension only ADDS entry points, so it is declared next to them
- * and read by alignq_amd/_lib.py into a table of its own (DENSE_SIGNATURES, bound last); nothing declared here appears in any other
+ * and read by alignq_amd/_lib.py into a table of its own (DENSE_SIGNATURES, bound fifth); nothing declared here appears in any other
  * header.  The header is plain C in the vocabulary alignq_amd/_header.py reads: prototypes over pointers and scalars, one POD record.
  *
  * A dense layer of the reference (cdf_alignment/dense-cifar-10/model/densenet.py:17-41) is bn1 -> act_q0 -> ReLU -> 3x3 convolution
