@@ -44,9 +44,14 @@ K3_FWD, K3_DGRAD, K3_WGRAD = (_K3CONV_CONSTANTS[n] for n in ("ALIGNQ_K3_FWD", "A
 DENSE_SIGNATURES, _DENSE_STRUCTS, _DENSE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_dense.h"))
 
 # K5CONV_SIGNATURES: the entry points of include/alignq_k5conv.h (the 5x5 / stride 1 / padding 0 Conv2d_Q convolutions with a bias:
-# the digit-domain DANN's two layers), a sixth table, bound last
+# the digit-domain DANN's two layers), a sixth table, bound after the five above
 K5CONV_SIGNATURES, _K5CONV_STRUCTS, _K5CONV_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k5conv.h"))
 K5_FWD, K5_DGRAD, K5_WGRAD = (_K5CONV_CONSTANTS[n] for n in ("ALIGNQ_K5_FWD", "ALIGNQ_K5_DGRAD", "ALIGNQ_K5_WGRAD"))
+
+# DIGIT_SIGNATURES: the entry points of include/alignq_digit.h (the digit DANN's evaluation: site and 2x2 max-pool as the 5x5
+# convolution's epilogue), a seventh table, bound last.  (Its record is alignq_dense.h's alignq_dense_site: DenseSite below.)
+DIGIT_SIGNATURES, _DIGIT_STRUCTS, _DIGIT_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_digit.h"))
+DIGIT_OUT_NHWC, DIGIT_OUT_FLAT_CHW = (_DIGIT_CONSTANTS[n] for n in ("ALIGNQ_DIGIT_OUT_NHWC", "ALIGNQ_DIGIT_OUT_FLAT_CHW"))
 
 
 class SiteBnArgs(ctypes.Structure):
@@ -93,7 +98,8 @@ def load():
                                   ("POINTWISE_SIGNATURES", "alignq_pointwise.h", "pointwise_kernels.hip"),
                                   ("K3CONV_SIGNATURES", "alignq_k3conv.h", "k3conv_kernels.hip"),
                                   ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip"),
-                                  ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip")):
+                                  ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip"),
+                                  ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

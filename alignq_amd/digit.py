@@ -12,6 +12,10 @@ Every weight and activation quantiser runs on this repository's kernels.  With u
 csrc/k5conv_kernels.hip (include/alignq_k5conv.h): the first on its image form (3 input channels folded with the 25 taps into one K),
 the second on its body form; batch-norm, ReLU, Dropout2d, the pools and the linear layers go to MIOpen / rocBLAS through PyTorch-ROCm.
 The sites run as the composition; training is eager iterations (train_iteration, with alignq_amd.optimizer.SGD).
+
+Evaluation (eval_step.EvalStep) with use_hip_convs(model, eval_fused=True): MNISTmodel_quant._forward_eval runs each half of `feature`
+as ONE alignq_k5conv_site_pool_eval_fwd launch (include/alignq_digit.h: eval-mode batch-norm, quantiser, ReLU and the 2 x 2 max-pool
+as the convolution's epilogue); the first reads the one-channel image directly, the second writes the classifier's (B, 768) matrix.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import cdf_alignment as _cdf
-from . import paths
+from . import fused, paths
 from .resnet_office import ReverseLayerF
 
 
@@ -36,6 +40,8 @@ def conv2d_Q5_fn(w_bit, stage):
 
 
 class MNISTmodel_quant(nn.Module):
+    fuse_digit_eval = False           # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+
     def __init__(self, stage, wbit, abit, img_size=28):
         super().__init__()
         self.restored = False
@@ -74,12 +80,41 @@ class MNISTmodel_quant(nn.Module):
         reverse_feature = ReverseLayerF.apply(feature, alpha)
         return self.classifier(feature), self.discriminator(reverse_feature)
 
+    # ---- evaluation (eval_step.EvalStep: the reference's test(), main.py:436-487 - eval mode, alpha = 0, the class logits) ----
+    def _half_eval(self, i, x, flat):
+        """feature[i : i + 5 or 6] on x in evaluation: conv 5x5 + bias, BN, act_q, (Dropout2d: the identity,) ReLU, MaxPool2d(2).  With
+        `fuse_digit_eval` one launch (fused.k5_site_pool_eval); where that returns None, or without the flag, the modules.  x may be
+        the one-channel image for the first half."""
+        conv, bn, act = self.feature[i], self.feature[i + 1], self.feature[i + 2]
+        y = fused.k5_site_pool_eval(conv, bn, act, x, flat=flat) if self.fuse_digit_eval and fused.eval_active() else None
+        if y is None:
+            if x.shape[1] != conv.in_channels:
+                x = x.expand(x.shape[0], conv.in_channels, x.shape[2], x.shape[3])
+                if conv.use_qconv_k5:
+                    x = x.contiguous(memory_format=torch.channels_last)
+            y = F.max_pool2d(F.relu(act(bn(conv(x)))), 2)
+            if flat:
+                y = y.reshape(y.shape[0], -1)          # (c, h, w) order whatever the layout
+        return y
 
-def use_hip_convs(model):
+    def _forward_eval(self, input_data):
+        """The class logits of forward(input_data, alpha) in eval mode (alpha only scales the reversed gradient; the domain head is not
+        evaluated).  The second half hands the classifier its (B, 768) matrix directly."""
+        if self.training:
+            raise RuntimeError("MNISTmodel_quant._forward_eval: the model is in training mode")
+        x = self._half_eval(0, input_data, False)
+        return self.classifier(self._half_eval(5, x, True))
+
+
+def use_hip_convs(model, eval_fused=False):
     """Channels-last parameters plus `use_qconv` and `use_qconv_k5`: both convolutions then run on alignq_k5conv_*, and `forward` hands
-    the first one a dense channels-last image.  Values, parameter names and state_dict are unchanged."""
+    the first one a dense channels-last image.  Values, parameter names and state_dict are unchanged.
+    eval_fused=True also sets `fuse_digit_eval`: inside eval_step.EvalStep each half of `feature` is then one launch
+    (include/alignq_digit.h); `forward` and every other launch are unchanged."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_k5=True)
+    if eval_fused:
+        paths.apply(model, fuse_digit_eval=True)
     return model
 
 

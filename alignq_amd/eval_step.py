@@ -20,7 +20,9 @@ itself inside the step (fused.site_eval_any / site_eval_twin / dw_site_eval, inc
 ReLU6, the stride-1 block tail, the depthwise convolution with its site as the epilogue).  densenet.DenseNet with
 `fuse_dense_eval` (densenet.use_hip_convs(model, dense_eval=True)) runs DenseNet._forward_eval inside the step: one buffer per dense
 block, every dense layer one launch with its site inside the 3x3 convolution (fused.dense_layer_eval, include/alignq_dense.h), no
-concatenation; without the flag a DenseNet runs today's composition.
+concatenation; without the flag a DenseNet runs today's composition.  digit.MNISTmodel_quant runs MNISTmodel_quant._forward_eval
+(the reference's test() of dann_digit/main.py:436-487: class logits at alpha = 0); with `fuse_digit_eval`
+(digit.use_hip_convs(model, eval_fused=True)) each half of `feature` is one launch (fused.k5_site_pool_eval, include/alignq_digit.h).
 
     ev = EvalStep(skeleton, weights=export.PackedModel.load(path))     # evaluate from packed k-bit codes (export.py): begin()
                                                                        # unpacks them; the model's fp32 filters are never read"""
@@ -36,7 +38,7 @@ from .train_step import _CapturedStep
 
 class EvalStep(_CapturedStep):
     """model: resnet.PreActResNet (tree "admm" or "cdf"), resnet_office.DANN (class logits at alpha = 0), resnet_office.DSAN
-    (s_pred), mobilenet.MobileNetV2 or densenet.DenseNet.  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
+    (s_pred), mobilenet.MobileNetV2, densenet.DenseNet or digit.MNISTmodel_quant (class logits at alpha = 0).  channels_last / qconv: as TrainStep / OfficeTrainStep (the folded evaluation sites need channels-last tensors;
     without it every site is today's `model.eval()` composition).  Nothing in model.state_dict() changes between begin() and
     end(); the module flags the step sets (fuse_bn, use_qconv, ...) and every training flag are put back by end()."""
 
@@ -52,7 +54,9 @@ class EvalStep(_CapturedStep):
         # the quantiser's launch also writes the convolutions' bf16 filter images: once per evaluation, read by every batch
         self.filter_images = bool(filter_images and self.qconv)
         self.all_convs = [m for m in model.modules() if hasattr(m, "quantize_fn")]
-        self._office = hasattr(model, "feature") or hasattr(model, "feature_layers")
+        from .digit import MNISTmodel_quant
+        self._digit = isinstance(model, MNISTmodel_quant)          # (it has a `.feature` too: recognised before the Office models)
+        self._office = not self._digit and (hasattr(model, "feature") or hasattr(model, "feature_layers"))
         self._acc = None             # include/alignq.h: {double sum ce, int64 top-1, int64 top-5, int64 rows}
         self._saved = None           # module flags and training modes to restore
         self._wq = None              # the parked quantised filters (persistent: a captured graph reads them)
@@ -68,9 +72,11 @@ class EvalStep(_CapturedStep):
     # ------------------------------------------------------------------------------------------- lifecycle
     def _pack_filters(self):
         """Whether begin() also leaves the filters' integer bins for the GEMM convolutions: the Office models, and any model whose
-        Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)) or `use_qconv_k3` (densenet.use_hip_convs: the
-        dense layers' launches read the parked bins) - once per evaluation, not per batch and layer"""
-        return self.qconv and (self._office or any(c.use_qconv_pw or getattr(c, "use_qconv_k3", False) for c in self.all_convs))
+        Conv2d_Q carry `use_qconv_pw` (mobilenet.use_hip_convs(model, pointwise=True)), `use_qconv_k3` (densenet.use_hip_convs: the
+        dense layers' launches read the parked bins) or `use_qconv_k5` (digit.use_hip_convs) - once per evaluation, not per batch and
+        layer"""
+        return self.qconv and (self._office or any(c.use_qconv_pw or getattr(c, "use_qconv_k3", False) or getattr(c, "use_qconv_k5", False)
+                                                   for c in self.all_convs))
 
     def _quantize_weights(self):
         """All filters once (fused.prequantize_weights; the GEMM convolutions' integer bins too), parked for every batch.  A second
@@ -146,6 +152,8 @@ class EvalStep(_CapturedStep):
     # ------------------------------------------------------------------------------------------- one batch
     def _logits(self, x):
         m = self.model
+        if self._digit:                                # the digit DANN: class logits at alpha = 0 (the domain head is not evaluated)
+            return m._forward_eval(x)
         if hasattr(m, "feature"):                      # DANN: class logits; alpha only scales the reversed gradient
             feature, _ = m.feature(x)
             return m.class_classifier(feature.view(-1, 2048))

@@ -1296,6 +1296,60 @@ def avgpool2_into(z, buf):
     return buf
 
 
+# The digit DANN's evaluation (include/alignq_digit.h, csrc/digit_eval_kernels.hip): each half of `feature` - conv 5x5 + bias, BN, act_q,
+# ReLU, MaxPool2d(2) - as one launch; the un-pooled tensor is never written.
+def k5_site_pool_eval(conv, bn, act, x, flat=False):
+    """max_pool2d(relu(act(bn.eval()(conv(x)))), 2) for a 5x5 / stride 1 / padding 0 Conv2d_Q with its bias by one
+    alignq_k5conv_site_pool_eval_fwd launch.  x: a channels-last fp32 CUDA tensor (B, C_in, H, W), or - for a 3-channel convolution - a
+    (B, 1, H, W) image, read directly for all three input channels.  Returns a channels-last (B, C_out, PH, PW) tensor, or with
+    flat=True the (B, C_out * PH * PW) matrix in (c, h, w) order (the reference's view(-1, 768)).  None where `use_qconv` / `use_qconv_k5`
+    are off, the filter is not parked with its bins (EvalStep.begin parks it), the batch-norm is not an eval-mode one with running
+    statistics over C_out channels, the quantiser has no folded form or the shape is outside the kernel's set."""
+    from . import config
+    if not (getattr(conv, "use_qconv", False) and getattr(conv, "use_qconv_k5", False) and torch.is_tensor(x) and x.dim() == 4
+            and x.is_cuda and x.dtype == torch.float32 and x.numel() > 0):
+        return None
+    q = conv.quantize_fn
+    w, w_bit = conv.weight, int(getattr(q, "w_bit", 32))
+    parked = q.parked
+    if parked is None or parked.weight is not w or parked.bins is None:
+        return None
+    B, xc, H, W = x.shape
+    cin, cout = int(conv.in_channels), int(conv.out_channels)
+    if xc == 1 and cin == 3:
+        if not x.is_contiguous():          # (a one-channel image is the same memory in both layouts)
+            return None
+    elif not (xc == cin and x.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    # the module is what alignq_k5conv_fwd takes (ops.qconv_k5_supported states it for a tensor of C_in channels)
+    if (conv.groups != 1 or not 1 <= w_bit <= 8 or tuple(conv.dilation) != (1, 1) or tuple(conv.stride) != (1, 1)
+            or tuple(conv.padding) != (0, 0) or tuple(w.shape) != (cout, cin, 5, 5)):
+        return None
+    bias = conv.bias
+    if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous()):
+        return None
+    lib = L.load()
+    if lib.alignq_k5conv_site_pool_eval_supported(B, H, W, cin, cout) != 1:
+        return None
+    kf = _eval_site(bn, act, cout)
+    if kf is None:
+        return None
+    PH, PW = (H - 4) // 2, (W - 4) // 2
+    if flat:
+        y = torch.empty((B, cout * PH * PW), dtype=torch.float32, device=x.device)
+    else:
+        y = torch.empty((B, cout, PH, PW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    site = L.DenseSite(L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var), float(bn.eps), int(kf[0]),
+                       int(CLAMP_RELU))
+    rc = lib.alignq_k5conv_site_pool_eval_fwd(L.ptr(x), int(xc), L.ptr(parked.bins[0]), L.ptr(conv.bias), ctypes.byref(site), L.ptr(y),
+                                              L.DIGIT_OUT_FLAT_CHW if flat else L.DIGIT_OUT_NHWC, B, H, W, cin, cout, w_bit,
+                                              float(config.args.act_range), int(kf[1]), L.stream_ptr())
+    L.check(rc, "alignq_k5conv_site_pool_eval_fwd")
+    return y
+
+
 def bn_only(bn, z, groups=1):
     """bn(z): the folded-family kernels when the tensor is channels-last fp32 in training mode, else the module itself
     (groups > 1: applied to the batch slices one after the other, as the reference's successive passes do)."""
