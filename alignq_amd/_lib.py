@@ -49,9 +49,14 @@ K5CONV_SIGNATURES, _K5CONV_STRUCTS, _K5CONV_CONSTANTS = _header.read(os.path.joi
 K5_FWD, K5_DGRAD, K5_WGRAD = (_K5CONV_CONSTANTS[n] for n in ("ALIGNQ_K5_FWD", "ALIGNQ_K5_DGRAD", "ALIGNQ_K5_WGRAD"))
 
 # DIGIT_SIGNATURES: the entry points of include/alignq_digit.h (the digit DANN's evaluation: site and 2x2 max-pool as the 5x5
-# convolution's epilogue), a seventh table, bound last.  (Its record is alignq_dense.h's alignq_dense_site: DenseSite below.)
+# convolution's epilogue), a seventh table.  (Its record is alignq_dense.h's alignq_dense_site: DenseSite below.)
 DIGIT_SIGNATURES, _DIGIT_STRUCTS, _DIGIT_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_digit.h"))
 DIGIT_OUT_NHWC, DIGIT_OUT_FLAT_CHW = (_DIGIT_CONSTANTS[n] for n in ("ALIGNQ_DIGIT_OUT_NHWC", "ALIGNQ_DIGIT_OUT_FLAT_CHW"))
+
+# K3IMAGE_SIGNATURES: the entry points of include/alignq_k3image.h (the 3x3 / stride 1 / padding 1 Conv2d_Q convolution of a 3-channel
+# image: DenseNet-40's and MobileNet-V2's stems), an eighth table, bound last
+K3IMAGE_SIGNATURES, _K3IMAGE_STRUCTS, _K3IMAGE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k3image.h"))
+K3I_FWD, K3I_WGRAD = (_K3IMAGE_CONSTANTS[n] for n in ("ALIGNQ_K3I_FWD", "ALIGNQ_K3I_WGRAD"))
 
 
 class SiteBnArgs(ctypes.Structure):
@@ -99,7 +104,8 @@ def load():
                                   ("K3CONV_SIGNATURES", "alignq_k3conv.h", "k3conv_kernels.hip"),
                                   ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip"),
                                   ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip"),
-                                  ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip")):
+                                  ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip"),
+                                  ("K3IMAGE_SIGNATURES", "alignq_k3image.h", "k3image_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

@@ -13,12 +13,13 @@ convolution in order; `indexes` is accepted and not read, as there).  densenet_4
 Every weight and activation quantiser runs on this repository's kernels.  With use_hip_convs(model) and channels-last inputs the 3x3
 dense layers (CIN = 24, 36, ..., 444 -> 12: multiples of 4, not of 8) run on csrc/k3conv_kernels.hip (include/alignq_k3conv.h) and
 the two transitions on csrc/pointwise_kernels.hip; the 3 -> 24 stem, batch-norm, the pools and the linear layer go to MIOpen /
-rocBLAS through PyTorch-ROCm.  The sites run as the composition; training is eager iterations (alignq_amd.optimizer.SGD).
+rocBLAS through PyTorch-ROCm.  With use_hip_convs(model, stem=True) the stem runs on csrc/k3image_kernels.hip
+(include/alignq_k3image.h) as well, and every Conv2d_Q of the model has arithmetic this repository defines.  The sites run as the composition; training is eager iterations (alignq_amd.optimizer.SGD).
 
 Evaluation (eval_step.EvalStep) with use_hip_convs(model, dense_eval=True): DenseNet._forward_eval keeps ONE buffer per dense block;
 a dense layer is one alignq_dense_layer_eval_fwd launch (include/alignq_dense.h: the site applied while the convolution stages its
 input, the 12 output channels written right behind the input), nothing is concatenated, and a transition's pool writes into the
-next block's buffer.
+next block's buffer.  With stem=True the stem writes into the first block's buffer itself (fused.stem_eval_into: one launch, no copy).
 """
 from __future__ import annotations
 
@@ -33,13 +34,15 @@ from . import fused, paths
 
 
 def conv2d_Q3_fn(w_bit, stage):
-    """Conv2d_Q of the CDF namespace plus one opt-in flag: with it the 3x3 / stride 1 / padding 1 convolutions at channel counts that
-    are multiples of 4 run on alignq_k3conv_*, ahead of every other family (ops.conv2d_q reads the flag).  The flag is declared HERE,
-    not on Conv2d_Q: no other model's modules carry it."""
+    """Conv2d_Q of the CDF namespace plus two opt-in flags: with `use_qconv_k3` the 3x3 / stride 1 / padding 1 convolutions at channel
+    counts that are multiples of 4 run on alignq_k3conv_*, ahead of every other family; with `use_qconv_k3_image` the one on the
+    3-channel image (the stem) runs on alignq_k3image_* (ops.conv2d_q reads the flags).  They are declared HERE, not on Conv2d_Q: no
+    other model's modules carry them."""
     base = _cdf.conv2d_Q_fn(w_bit=w_bit, stage=stage)
 
     class Conv2d_Q3(base):
         use_qconv_k3 = False          # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+        use_qconv_k3_image = False    # likewise
 
     return Conv2d_Q3
 
@@ -138,11 +141,11 @@ class DenseNet(nn.Module):
     # ---- evaluation without concatenations (inside fused.eval_scope: eval_step.EvalStep) ----
     def _forward_eval(self, x):
         """forward() with one buffer per dense block (168 / 312 / 456 channels at depth 40): the block's input is copied into its
-        first channels once, every dense layer is one launch in place (fused.dense_layer_eval), a transition is its site on the full
+        first channels once (with `use_qconv_k3_image` the stem writes them itself: _stem_eval), every dense layer is one launch in place (fused.dense_layer_eval), a transition is its site on the full
         buffer (fused.site_eval_any), the 1x1 convolution and the pool into the next block's buffer (fused.avgpool2_into), the head its
         site, the pool and the linear layer.  Whatever has no kernel runs the composition of forward().  Dropout is inactive in
         evaluation."""
-        x = self._dense_eval(self.dense1, self.conv1(x), None)
+        x = self._dense_eval(self.dense1, *self._stem_eval(x))
         x = self._dense_eval(self.dense2, *self._transition_eval(self.trans1, x, self.dense2))
         x = self._dense_eval(self.dense3, *self._transition_eval(self.trans2, x, self.dense3))
         y = fused.site_eval_any(self.bn, self.act_q0, x, fused.CLAMP_RELU)
@@ -150,6 +153,16 @@ class DenseNet(nn.Module):
             y = self.relu(self.act_q0(self.bn(x)))
         x = self.avgpool(y)
         return self.fc(x.reshape(x.size(0), -1))
+
+    def _stem_eval(self, x):
+        """(conv1(x), None), or (None, buf) with the stem's output in the first channels of the first block's buffer"""
+        dense = self.dense1
+        if (getattr(self.conv1, "use_qconv_k3_image", False) and len(dense) and not self.training and fused._nhwc_f32(x)
+                and self.conv1.out_channels == dense[0].bn1.num_features):
+            buf = self._block_buffer(dense, x.shape[0], x.shape[2], x.shape[3], x.device)
+            if fused.stem_eval_into(self.conv1, x, buf) is not None:
+                return None, buf
+        return self.conv1(x), None
 
     @staticmethod
     def _block_buffer(dense, B, H, W, device):
@@ -190,14 +203,18 @@ def densenet_40_quant(bitW, abitW, stage, pretrained=False, **kwargs):
     return DenseNet(wbit=bitW, abit=abitW, stage=stage, depth=40, block=DenseBasicBlock, compressionRate=1, **kwargs)
 
 
-def use_hip_convs(model, dense_eval=False):
+def use_hip_convs(model, dense_eval=False, stem=False):
     """Channels-last parameters plus `use_qconv`, `use_qconv_pw` (the transitions) and `use_qconv_k3` (the dense layers): with
     channels-last inputs every dense layer then runs on alignq_k3conv_* and both transitions on alignq_pwconv_*; the concatenations keep
     the layout, so no dense layer falls back to MIOpen.  Values, parameter names and state_dict are unchanged.
     dense_eval=True also sets `fuse_dense_eval`: inside eval_step.EvalStep the model then runs DenseNet._forward_eval (one launch per
-    dense layer, no concatenation); every other forward is unchanged."""
+    dense layer, no concatenation); every other forward is unchanged.
+    stem=True also sets `use_qconv_k3_image`: the 3 -> 24 stem then runs on alignq_k3image_*, and inside _forward_eval it writes into
+    the first block's buffer by one launch.  Without it every launch is what it was."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_pw=True, use_qconv_k3=True)
+    if stem:
+        paths.apply(model, use_qconv_k3_image=True)
     if dense_eval:
         paths.apply(model, fuse_dense_eval=True)
     return model

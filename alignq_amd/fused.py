@@ -1281,6 +1281,31 @@ def dense_layer_eval(conv, bn, act, buf, cin):
     return buf
 
 
+def stem_eval_into(conv, x, buf):
+    """buf[:, :C_out] = conv(x) for the 3x3 / stride 1 / padding 1 Conv2d_Q of a 3-channel image by one alignq_k3image_fwd launch at
+    the buffer's pitch (include/alignq_k3image.h): the stem's output is never written anywhere else and nothing is copied.  Returns buf.
+    None where `use_qconv` / `use_qconv_k3_image` are off, the filter is not parked with its bins (EvalStep.begin parks it), x is not a
+    channels-last fp32 CUDA image that needs no gradient, buf is not a channels-last fp32 CUDA tensor of x's batch, height and width
+    with room for the output, or the shape is outside alignq_k3image_fwd's set."""
+    from . import ops
+    if not (getattr(conv, "use_qconv", False) and getattr(conv, "use_qconv_k3_image", False) and _nhwc_f32(x) and _nhwc_f32(buf)):
+        return None
+    q = conv.quantize_fn
+    w, w_bit = conv.weight, int(getattr(q, "w_bit", 32))
+    parked = q.parked
+    if parked is None or parked.weight is not w or parked.bins is None:
+        return None
+    B, C_end, H, W = buf.shape
+    cout = int(conv.out_channels)
+    if tuple(x.shape) != (B, 3, H, W) or cout > C_end or C_end % 4 or B * H * W * C_end > 2 ** 31 - 1:
+        return None
+    if not ops.qconv_k3_image_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, w_bit):
+        return None
+    rc = L.load().alignq_k3image_fwd(L.ptr(x), L.ptr(parked.bins[0]), L.ptr(buf), B, H, W, cout, C_end, w_bit, L.stream_ptr())
+    L.check(rc, "alignq_k3image_fwd")
+    return buf
+
+
 def avgpool2_into(z, buf):
     """buf[:, :C] = F.avg_pool2d(z, 2) by one alignq_avgpool2_nhwc_fwd launch (the window summed row-major, then * 0.25); z (B, C, H, W)
     and buf (B, C_end >= C, H // 2, W // 2) channels-last fp32 CUDA tensors.  Returns buf, or None where the kernel does not apply."""

@@ -1337,6 +1337,59 @@ class QConvK5Fn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+def qconv_k3_image_supported(x, w, stride, padding, dilation, groups, bias, w_bit) -> bool:
+    """The stem convolutions alignq_k3image_* take (include/alignq_k3image.h; DenseNet-40's and MobileNet-V2's conv1): a (C_out, 3, 3, 3)
+    channels-last CUDA fp32 filter, stride 1, padding 1, dilation 1, groups 1, no bias, <= 8-bit quantised filter, C_out a multiple of 4
+    in [4, 512], a channels-last fp32 input of 3 channels that needs no gradient (the family has no data gradient)."""
+    if not _quantised_conv(dilation, groups, bias, w_bit) or tuple(stride) != (1, 1) or tuple(padding) != (1, 1):
+        return False
+    if not (_nhwc_input(x) and x.shape[1] == 3 and not x.requires_grad):
+        return False
+    if not (_cuda_f32(w) and w.dim() == 4 and tuple(w.shape[1:]) == (3, 3, 3) and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    B, _, H, W = x.shape
+    lib = L.load()
+    return all(lib.alignq_k3image_supported(op, B, H, W, w.shape[0]) == 1 for op in (L.K3I_FWD, L.K3I_WGRAD))
+
+
+class QConvK3ImageFn(torch.autograd.Function):
+    """F.conv2d(image, weight_q, None, 1, 1) of Conv2d_Q.forward for a (C_out, 3, 3, 3) filter, on alignq_k3image_fwd / _wgrad
+    (csrc/k3image_kernels.hip): exact products of the filter's integer bins and three bf16 terms of the fp32 image, taps and channels
+    folded into one MFMA k step.  bins: as QConvK3Fn's.  The image gets no gradient; the filter gradient's slab reduction is deferred
+    to fused.DeferredWgrads when such a context is active.  (Its own forward and backward, not _bins_conv_*: no data gradient, no CIN
+    and an output pitch among the arguments.)"""
+
+    @staticmethod
+    def forward(ctx, x, w, w_bit, bins=None):
+        if bins is None:
+            bins = pack_filter_bins([w], w_bit)[0]
+        B, _, H, W = x.shape
+        COUT = w.shape[0]
+        y = torch.empty((B, COUT, H, W), dtype=torch.float32, device=w.device, memory_format=torch.channels_last)
+        L.check(L.load().alignq_k3image_fwd(L.ptr(x), L.ptr(bins[0]), L.ptr(y), B, H, W, COUT, COUT, int(w_bit), L.stream_ptr()),
+                "alignq_k3image_fwd")
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("QConvK3ImageFn: the image form has no data gradient (qconv_k3_image_supported refuses such an input)")
+        dw = None
+        if ctx.needs_input_grad[1]:
+            lib = L.load()
+            if not gy.is_contiguous(memory_format=torch.channels_last):
+                gy = gy.contiguous(memory_format=torch.channels_last)
+            B, _, H, W = x.shape
+            geom = (B, H, W, w.shape[0])
+            dw = torch.empty_like(w)
+            ws = _ws(lib.alignq_k3image_wgrad_ws_bytes(*geom), w.device)
+            _filter_grad(ws, dw, w.numel(), lambda dwp, nsp: L.check(lib.alignq_k3image_wgrad(
+                L.ptr(x), L.ptr(gy), dwp, L.ptr(ws), *geom, nsp, L.stream_ptr()), "alignq_k3image_wgrad"))
+        return None, dw, None, None
+
+
 # ------------------------------------------------------------------------------------------------ which family a convolution gets
 def _gemm_node(conv, x, w, w_bit, bins, xbins=None):
     """The GEMM family with or without the batch-norm statistics of its output (emit_bn_stats: the batch-norm behind this convolution
@@ -1361,6 +1414,8 @@ def conv2d_q(conv, x, w, tap=False):
       3. QConvK3Fn      3x3 at multiples of 4, only where the module declares and sets use_qconv_k3 (densenet.Conv2d_Q3)
       3a. QConvK5Fn     5x5 / padding 0 with or without a bias, 3 or a multiple of 4 input channels, only where the module declares
                         and sets use_qconv_k5 (digit.Conv2d_Q5); the one family that takes a bias
+      3b. QConvK3ImageFn  3x3 / padding 1 on a 3-channel image that needs no gradient (the stem), only where the module declares and
+                        sets use_qconv_k3_image (densenet.Conv2d_Q3)
       4. QConv3x3Fn     the ResNet-20/56 body
       5. QConvGenFn     the stride-2 transition convolutions
       6. QConvStemFn    3 -> 16
@@ -1389,6 +1444,8 @@ def conv2d_q(conv, x, w, tap=False):
             return QConvK3Fn.apply(x, w, w_bit, rec.bins)
         if packed is None and not tap and getattr(conv, "use_qconv_k5", False) and qconv_k5_supported(x, *args):
             return QConvK5Fn.apply(x, w, conv.bias, w_bit, rec.bins)
+        if packed is None and not tap and getattr(conv, "use_qconv_k3_image", False) and qconv_k3_image_supported(x, *args):
+            return QConvK3ImageFn.apply(x, w, w_bit, rec.bins)
         # (4 - 6 with the batch-norm statistics of the output as a by-product for fused.bn_site)
         if qconv3x3_supported(x, *args):
             return QConv3x3Fn.apply_with_stats(x, w, w_bit, tap, img=rec.image)
