@@ -58,6 +58,10 @@ DIGIT_OUT_NHWC, DIGIT_OUT_FLAT_CHW = (_DIGIT_CONSTANTS[n] for n in ("ALIGNQ_DIGI
 K3IMAGE_SIGNATURES, _K3IMAGE_STRUCTS, _K3IMAGE_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_k3image.h"))
 K3I_FWD, K3I_WGRAD = (_K3IMAGE_CONSTANTS[n] for n in ("ALIGNQ_K3I_FWD", "ALIGNQ_K3I_WGRAD"))
 
+# BNQANY_SIGNATURES: the entry points of include/alignq_bnq_any.h (training-mode batch-norm folded into the plain quantiser and a clamp
+# at any channel count that is a multiple of 4: MobileNet-V2's and DenseNet-40's site widths), a ninth table, bound last
+BNQANY_SIGNATURES, _BNQANY_STRUCTS, _BNQANY_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_bnq_any.h"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -105,7 +109,8 @@ def load():
                                   ("DENSE_SIGNATURES", "alignq_dense.h", "dense_eval_kernels.hip"),
                                   ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip"),
                                   ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip"),
-                                  ("K3IMAGE_SIGNATURES", "alignq_k3image.h", "k3image_kernels.hip")):
+                                  ("K3IMAGE_SIGNATURES", "alignq_k3image.h", "k3image_kernels.hip"),
+                                  ("BNQANY_SIGNATURES", "alignq_bnq_any.h", "bnq_any_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

@@ -14,7 +14,9 @@ Every weight and activation quantiser runs on this repository's kernels.  With u
 dense layers (CIN = 24, 36, ..., 444 -> 12: multiples of 4, not of 8) run on csrc/k3conv_kernels.hip (include/alignq_k3conv.h) and
 the two transitions on csrc/pointwise_kernels.hip; the 3 -> 24 stem, batch-norm, the pools and the linear layer go to MIOpen /
 rocBLAS through PyTorch-ROCm.  With use_hip_convs(model, stem=True) the stem runs on csrc/k3image_kernels.hip
-(include/alignq_k3image.h) as well, and every Conv2d_Q of the model has arithmetic this repository defines.  The sites run as the composition; training is eager iterations (alignq_amd.optimizer.SGD).
+(include/alignq_k3image.h) as well, and every Conv2d_Q of the model has arithmetic this repository defines.  The sites run as the
+composition, or, with use_hip_convs(model, train_sites=True), folded in training: batch-norm, quantiser and ReLU as three launches each way
+on csrc/bnq_any_kernels.hip (include/alignq_bnq_any.h) at every width.  Training is eager iterations (alignq_amd.optimizer.SGD).
 
 Evaluation (eval_step.EvalStep) with use_hip_convs(model, dense_eval=True): DenseNet._forward_eval keeps ONE buffer per dense block;
 a dense layer is one alignq_dense_layer_eval_fwd launch (include/alignq_dense.h: the site applied while the convolution stages its
@@ -47,7 +49,20 @@ def conv2d_Q3_fn(w_bit, stage):
     return Conv2d_Q3
 
 
+def _site(mod, bn, act, x):
+    """relu(act(bn(x))).  With the module's `fuse_train_sites` on, a training forward runs it as one folded chain at any channel count
+    (fused.bn_act_any: three launches each way, the normalised activation never written); where that does not apply, and always with
+    the flag off, it is the composition."""
+    if mod.fuse_train_sites and mod.training and not fused.eval_active():
+        out = fused.bn_act_any(bn, act, x, fused.CLAMP_RELU)
+        if out is not None:
+            return out
+    return mod.relu(act(bn(x)))
+
+
 class DenseBasicBlock(nn.Module):
+    fuse_train_sites = False          # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+
     def __init__(self, stage, wbit, abit, inplanes, filters, index, expansion=1, growthRate=12, dropRate=0):
         super().__init__()
         Conv2d = conv2d_Q3_fn(w_bit=wbit, stage=stage)
@@ -58,13 +73,15 @@ class DenseBasicBlock(nn.Module):
         self.dropRate = dropRate
 
     def forward(self, x):
-        out = self.conv1(self.relu(self.act_q0(self.bn1(x))))
+        out = self.conv1(_site(self, self.bn1, self.act_q0, x))
         if self.dropRate > 0:
             out = F.dropout(out, p=self.dropRate, training=self.training)
         return torch.cat((x, out), 1)          # channels-last inputs give a channels-last result
 
 
 class Transition(nn.Module):
+    fuse_train_sites = False          # likewise
+
     def __init__(self, stage, wbit, abit, inplanes, outplanes, filters, index):
         super().__init__()
         Conv2d = _cdf.conv2d_Q_fn(w_bit=wbit, stage=stage)
@@ -74,11 +91,12 @@ class Transition(nn.Module):
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
-        return F.avg_pool2d(self.conv1(self.relu(self.act_q0(self.bn1(x)))), 2)
+        return F.avg_pool2d(self.conv1(_site(self, self.bn1, self.act_q0, x)), 2)
 
 
 class DenseNet(nn.Module):
     fuse_dense_eval = False           # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+    fuse_train_sites = False          # likewise
 
     def __init__(self, wbit, abit, stage, depth=40, block=DenseBasicBlock, dropRate=0, num_classes=10, growthRate=12,
                  compressionRate=2, filters=None, indexes=None):
@@ -134,7 +152,7 @@ class DenseNet(nn.Module):
         x = self.dense1(self.conv1(x))
         x = self.dense2(self.trans1(x))
         x = self.dense3(self.trans2(x))
-        x = self.avgpool(self.relu(self.act_q0(self.bn(x))))
+        x = self.avgpool(_site(self, self.bn, self.act_q0, x))
         return self.fc(x.reshape(x.size(0), -1))
 
 
@@ -203,18 +221,22 @@ def densenet_40_quant(bitW, abitW, stage, pretrained=False, **kwargs):
     return DenseNet(wbit=bitW, abit=abitW, stage=stage, depth=40, block=DenseBasicBlock, compressionRate=1, **kwargs)
 
 
-def use_hip_convs(model, dense_eval=False, stem=False):
+def use_hip_convs(model, dense_eval=False, stem=False, train_sites=False):
     """Channels-last parameters plus `use_qconv`, `use_qconv_pw` (the transitions) and `use_qconv_k3` (the dense layers): with
     channels-last inputs every dense layer then runs on alignq_k3conv_* and both transitions on alignq_pwconv_*; the concatenations keep
     the layout, so no dense layer falls back to MIOpen.  Values, parameter names and state_dict are unchanged.
     dense_eval=True also sets `fuse_dense_eval`: inside eval_step.EvalStep the model then runs DenseNet._forward_eval (one launch per
     dense layer, no concatenation); every other forward is unchanged.
     stem=True also sets `use_qconv_k3_image`: the 3 -> 24 stem then runs on alignq_k3image_*, and inside _forward_eval it writes into
-    the first block's buffer by one launch.  Without it every launch is what it was."""
+    the first block's buffer by one launch.  Without it every launch is what it was.
+    train_sites=True also sets `fuse_train_sites`: in training forwards every bn -> act_q0 -> ReLU site (dense layers, transitions, head)
+    then runs folded on alignq_bnq_any_* (include/alignq_bnq_any.h).  Without it every launch is what it was."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_pw=True, use_qconv_k3=True)
     if stem:
         paths.apply(model, use_qconv_k3_image=True)
     if dense_eval:
         paths.apply(model, fuse_dense_eval=True)
+    if train_sites:
+        paths.apply(model, fuse_train_sites=True)
     return model

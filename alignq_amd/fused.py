@@ -947,6 +947,67 @@ def bnq_fusable(bn, act, z, groups=1) -> bool:
     return _bn_nhwc_ok(bn, z, groups) and act.a_bit < 32
 
 
+# ---- the same fold at ANY channel count C % 4 == 0 (include/alignq_bnq_any.h, csrc/bnq_any_kernels.hip) ----
+# `clamp(act_q(bn(z)))` of mobilenetV2.py:55-69 / :114-125 and densenet.py:31-34 / :56-59 / :148-150, clamp = none, ReLU or ReLU6: three
+# launches each way, 12 B per element forward and about 20 B backward; one slice, no residual, no packed output.
+class BNQuantAnyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, weight, bias, running_mean, running_var, nbt, momentum, bn_eps, k, act_range, formula, clamp):
+        z = L.dense_f32(z, "conv output")
+        B, C, H, W = z.shape
+        P = B * H * W
+        lib, dev = L.load(), z.device
+        ab = torch.empty(2, C, dtype=torch.float32, device=dev)
+        save = torch.empty(2, C, dtype=torch.float32, device=dev)
+        y = torch.empty_like(z)
+        ws = torch.empty(lib.alignq_bnq_any_ws_bytes(P, C), dtype=torch.uint8, device=dev)
+        # one bit per element, "the gradient passes" (0 < y, below 6 under ReLU6): what the backward reads instead of y
+        mask = torch.empty(lib.alignq_bnq_any_mask_bytes(P, C), dtype=torch.uint8, device=dev) if clamp != CLAMP_NONE else None
+        L.check(lib.alignq_bnq_any_fwd(L.ptr(z), P, C, L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt),
+                                       float(momentum), float(bn_eps), int(k), float(act_range), int(formula), int(clamp), L.ptr(ab),
+                                       L.ptr(save), L.ptr(y), L.ptr(mask), L.ptr(ws), L.stream_ptr()),
+                "alignq_bnq_any_fwd")
+        ctx.save_for_backward(z, mask, ab, save)
+        ctx.cfg = (float(act_range), int(clamp), weight is not None, bias is not None)
+        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var, nbt) if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, mask, ab, save = ctx.saved_tensors
+        act_range, clamp, has_w, has_b = ctx.cfg
+        B, C, H, W = z.shape
+        P = B * H * W
+        g = L.like_layout(g, z)
+        lib = L.load()
+        dz = torch.empty_like(z)
+        dgamma = torch.empty(C, dtype=torch.float32, device=z.device) if has_w else None
+        dbeta = torch.empty(C, dtype=torch.float32, device=z.device) if has_b else None
+        ws = torch.empty(lib.alignq_bnq_any_ws_bytes(P, C), dtype=torch.uint8, device=z.device)
+        L.check(lib.alignq_bnq_any_bwd(L.ptr(g), L.ptr(z), L.ptr(mask), L.ptr(ab), L.ptr(save), P, C, act_range, clamp, L.ptr(dz),
+                                       L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), L.stream_ptr()),
+                "alignq_bnq_any_bwd")
+        return dz, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+
+
+def bn_act_any(bn, act, z, clamp):
+    """clamp(act(bn(z))) by BNQuantAnyFn, or None where it does not apply (the caller composes): a training nn.BatchNorm2d with tracked
+    statistics and a momentum, z a channels-last fp32 CUDA tensor, a plain quantiser (no ADMM term) with a_bit < 32, and a (P, C)
+    alignq_bnq_any_supported accepts."""
+    from . import config
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.track_running_stats and bn.momentum is not None
+            and bn.running_mean is not None and _nhwc_f32(z) and z.shape[1] == bn.num_features):
+        return None
+    formula = getattr(act, "_formula", None)
+    if not (1 <= int(getattr(act, "a_bit", 32)) <= 16 and formula in (L.FORMULA_ADMM, L.FORMULA_CDF) and not hasattr(act, "opt")):
+        return None
+    B, C, H, W = z.shape
+    if L.load().alignq_bnq_any_supported(B * H * W, C) != 1:
+        return None
+    return BNQuantAnyFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                              act.a_bit, config.args.act_range, formula, clamp)
+
+
 class BNAffineFn(torch.autograd.Function):
     """Training-mode nn.BatchNorm2d alone on a channels-last tensor (the Office bottleneck's downsample branch,
     dann_office/model/resnet.py:122-126): alignq_bnq_stats + alignq_bnq_affine forward, alignq_bnq_bwd_dx backward.
