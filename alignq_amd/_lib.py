@@ -59,8 +59,12 @@ K3IMAGE_SIGNATURES, _K3IMAGE_STRUCTS, _K3IMAGE_CONSTANTS = _header.read(os.path.
 K3I_FWD, K3I_WGRAD = (_K3IMAGE_CONSTANTS[n] for n in ("ALIGNQ_K3I_FWD", "ALIGNQ_K3I_WGRAD"))
 
 # BNQANY_SIGNATURES: the entry points of include/alignq_bnq_any.h (training-mode batch-norm folded into the plain quantiser and a clamp
-# at any channel count that is a multiple of 4: MobileNet-V2's and DenseNet-40's site widths), a ninth table, bound last
+# at any channel count that is a multiple of 4: MobileNet-V2's and DenseNet-40's site widths), a ninth table
 BNQANY_SIGNATURES, _BNQANY_STRUCTS, _BNQANY_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_bnq_any.h"))
+
+# BNQPOOL_SIGNATURES: the entry points of include/alignq_bnq_pool.h (training-mode batch-norm folded into the plain quantiser, a ReLU
+# and a 2 x 2 max-pool: the digit DANN's two training sites), a tenth table, bound last
+BNQPOOL_SIGNATURES, _BNQPOOL_STRUCTS, _BNQPOOL_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_bnq_pool.h"))
 
 
 class SiteBnArgs(ctypes.Structure):
@@ -110,7 +114,8 @@ def load():
                                   ("K5CONV_SIGNATURES", "alignq_k5conv.h", "k5conv_kernels.hip"),
                                   ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip"),
                                   ("K3IMAGE_SIGNATURES", "alignq_k3image.h", "k3image_kernels.hip"),
-                                  ("BNQANY_SIGNATURES", "alignq_bnq_any.h", "bnq_any_kernels.hip")):
+                                  ("BNQANY_SIGNATURES", "alignq_bnq_any.h", "bnq_any_kernels.hip"),
+                                  ("BNQPOOL_SIGNATURES", "alignq_bnq_pool.h", "bnq_pool_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

@@ -11,7 +11,9 @@ gradient reversal, to the domain head; forward(input_data, alpha) expands a 1-ch
 Every weight and activation quantiser runs on this repository's kernels.  With use_hip_convs(model) the two convolutions run on
 csrc/k5conv_kernels.hip (include/alignq_k5conv.h): the first on its image form (3 input channels folded with the 25 taps into one K),
 the second on its body form; batch-norm, ReLU, Dropout2d, the pools and the linear layers go to MIOpen / rocBLAS through PyTorch-ROCm.
-The sites run as the composition; training is eager iterations (train_iteration, with alignq_amd.optimizer.SGD).
+The sites run as the composition, or with use_hip_convs(model, train_sites=True) each as one fused.BNQuantPoolFn node
+(include/alignq_bnq_pool.h: batch-norm, quantiser, ReLU and the 2 x 2 max-pool folded, three launches each way); training is eager
+iterations (train_iteration, with alignq_amd.optimizer.SGD).
 
 Evaluation (eval_step.EvalStep) with use_hip_convs(model, eval_fused=True): MNISTmodel_quant._forward_eval runs each half of `feature`
 as ONE alignq_k5conv_site_pool_eval_fwd launch (include/alignq_digit.h: eval-mode batch-norm, quantiser, ReLU and the 2 x 2 max-pool
@@ -41,6 +43,7 @@ def conv2d_Q5_fn(w_bit, stage):
 
 class MNISTmodel_quant(nn.Module):
     fuse_digit_eval = False           # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
+    fuse_train_sites = False          # likewise
 
     def __init__(self, stage, wbit, abit, img_size=28):
         super().__init__()
@@ -75,10 +78,27 @@ class MNISTmodel_quant(nn.Module):
         if self.feature[0].use_qconv_k5:
             # the kernels read a dense channels-last image (the expanded view has a channel stride of 0)
             input_data = input_data.contiguous(memory_format=torch.channels_last)
-        feature = self.feature(input_data)
+        if self.fuse_train_sites and self.training and not fused.eval_active():
+            feature = self._half_train(5, self._half_train(0, input_data))
+        else:
+            feature = self.feature(input_data)
         feature = feature.reshape(-1, 48 * 4 * 4)          # (c, h, w) order whatever the layout, as the reference's view
         reverse_feature = ReverseLayerF.apply(feature, alpha)
         return self.classifier(feature), self.discriminator(reverse_feature)
+
+    def _half_train(self, i, x):
+        """feature[i : i + 5 or 6] on x in training with `fuse_train_sites`: the convolution, then BN -> act_q -> ReLU -> MaxPool2d(2)
+        as one fused.BNQuantPoolFn node (include/alignq_bnq_pool.h); where fused.bn_act_pool returns None, the modules.  The second
+        half's Dropout2d runs on the POOLED tensor: its noise is one draw per (sample, channel), independent of H x W, and scaling a
+        whole channel by 0 or 2 commutes with ReLU and with the window maximum, so the values are those of the reference's order
+        (a zero may differ in sign)."""
+        f = self.feature
+        z = f[i](x)
+        drop = f[i + 3] if isinstance(f[i + 3], nn.Dropout2d) else None
+        y = fused.bn_act_pool(f[i + 1], f[i + 2], z)
+        if y is None:
+            return f[i + 1:i + (6 if drop is not None else 5)](z)
+        return y if drop is None else drop(y)
 
     # ---- evaluation (eval_step.EvalStep: the reference's test(), main.py:436-487 - eval mode, alpha = 0, the class logits) ----
     def _half_eval(self, i, x, flat):
@@ -106,15 +126,19 @@ class MNISTmodel_quant(nn.Module):
         return self.classifier(self._half_eval(5, x, True))
 
 
-def use_hip_convs(model, eval_fused=False):
+def use_hip_convs(model, eval_fused=False, train_sites=False):
     """Channels-last parameters plus `use_qconv` and `use_qconv_k5`: both convolutions then run on alignq_k5conv_*, and `forward` hands
     the first one a dense channels-last image.  Values, parameter names and state_dict are unchanged.
     eval_fused=True also sets `fuse_digit_eval`: inside eval_step.EvalStep each half of `feature` is then one launch
-    (include/alignq_digit.h); `forward` and every other launch are unchanged."""
+    (include/alignq_digit.h); `forward` and every other launch are unchanged.
+    train_sites=True also sets `fuse_train_sites`: in training forwards each BN -> act_q -> [Dropout2d ->] ReLU -> MaxPool2d(2) of
+    `feature` is one fused.BNQuantPoolFn node (include/alignq_bnq_pool.h), Dropout2d applied to the pooled tensor."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_k5=True)
     if eval_fused:
         paths.apply(model, fuse_digit_eval=True)
+    if train_sites:
+        paths.apply(model, fuse_train_sites=True)
     return model
 
 

@@ -1008,6 +1008,67 @@ def bn_act_any(bn, act, z, clamp):
                               act.a_bit, config.args.act_range, formula, clamp)
 
 
+# ---- the fold with a ReLU and a 2 x 2 max-pool behind it (include/alignq_bnq_pool.h, csrc/bnq_pool_kernels.hip) ----
+# `MaxPool2d(2)(ReLU(act_q(bn(z))))` of dann_digit/model/dann.py's `feature`: three launches each way; the backward's statistics read the
+# pooled elements only, and neither the un-pooled output nor the un-pooled gradient is ever written.
+class BNQuantPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, weight, bias, running_mean, running_var, nbt, momentum, bn_eps, k, act_range, formula):
+        z = L.dense_f32(z, "conv output")
+        B, C, H, W = z.shape
+        lib, dev = L.load(), z.device
+        ab = torch.empty(2, C, dtype=torch.float32, device=dev)
+        save = torch.empty(2, C, dtype=torch.float32, device=dev)
+        y = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        ws = torch.empty(lib.alignq_bnq_pool_ws_bytes(B, H, W, C), dtype=torch.uint8, device=dev)
+        # one byte per pooled element: the window position of the first maximum and "the gradient passes" (y > 0)
+        code = torch.empty(lib.alignq_bnq_pool_code_bytes(B, H, W, C), dtype=torch.uint8, device=dev)
+        L.check(lib.alignq_bnq_pool_fwd(L.ptr(z), B, H, W, C, L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var),
+                                        L.ptr(nbt), float(momentum), float(bn_eps), int(k), float(act_range), int(formula), L.ptr(ab),
+                                        L.ptr(save), L.ptr(y), L.ptr(code), L.ptr(ws), L.stream_ptr()),
+                "alignq_bnq_pool_fwd")
+        ctx.save_for_backward(z, code, ab, save)
+        ctx.cfg = (float(act_range), weight is not None, bias is not None)
+        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var, nbt) if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, code, ab, save = ctx.saved_tensors
+        act_range, has_w, has_b = ctx.cfg
+        B, C, H, W = z.shape
+        if not g.is_cuda or g.dtype != torch.float32:
+            raise TypeError("alignq_amd: the pooled site's grad must be a CUDA float32 tensor")
+        g = g.contiguous(memory_format=torch.channels_last)
+        lib = L.load()
+        dz = torch.empty_like(z)
+        dgamma = torch.empty(C, dtype=torch.float32, device=z.device) if has_w else None
+        dbeta = torch.empty(C, dtype=torch.float32, device=z.device) if has_b else None
+        ws = torch.empty(lib.alignq_bnq_pool_ws_bytes(B, H, W, C), dtype=torch.uint8, device=z.device)
+        L.check(lib.alignq_bnq_pool_bwd(L.ptr(g), L.ptr(z), L.ptr(code), L.ptr(ab), L.ptr(save), B, H, W, C, act_range, L.ptr(dz),
+                                        L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), L.stream_ptr()),
+                "alignq_bnq_pool_bwd")
+        return dz, dgamma, dbeta, None, None, None, None, None, None, None, None
+
+
+def bn_act_pool(bn, act, z):
+    """max_pool2d(relu(act(bn(z))), 2) by BNQuantPoolFn, or None where it does not apply (the caller composes): a training
+    nn.BatchNorm2d with tracked statistics and a momentum, z a dense channels-last fp32 CUDA tensor, a plain quantiser (no ADMM term)
+    with a_bit <= 16, and a (B, H, W, C) alignq_bnq_pool_supported accepts."""
+    from . import config
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.track_running_stats and bn.momentum is not None
+            and bn.running_mean is not None and _nhwc_f32(z) and z.shape[1] == bn.num_features):
+        return None
+    formula = getattr(act, "_formula", None)
+    if not (1 <= int(getattr(act, "a_bit", 32)) <= 16 and formula in (L.FORMULA_ADMM, L.FORMULA_CDF) and not hasattr(act, "opt")):
+        return None
+    B, C, H, W = z.shape
+    if L.load().alignq_bnq_pool_supported(B, H, W, C) != 1:
+        return None
+    return BNQuantPoolFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                               act.a_bit, config.args.act_range, formula)
+
+
 class BNAffineFn(torch.autograd.Function):
     """Training-mode nn.BatchNorm2d alone on a channels-last tensor (the Office bottleneck's downsample branch,
     dann_office/model/resnet.py:122-126): alignq_bnq_stats + alignq_bnq_affine forward, alignq_bnq_bwd_dx backward.
