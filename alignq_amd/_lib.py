@@ -66,6 +66,11 @@ BNQANY_SIGNATURES, _BNQANY_STRUCTS, _BNQANY_CONSTANTS = _header.read(os.path.joi
 # and a 2 x 2 max-pool: the digit DANN's two training sites), a tenth table, bound last
 BNQPOOL_SIGNATURES, _BNQPOOL_STRUCTS, _BNQPOOL_CONSTANTS = _header.read(os.path.join(_HERE, "..", "include", "alignq_bnq_pool.h"))
 
+# DENSETRAIN_SIGNATURES: the entry points of include/alignq_dense_train.h (DenseNet's dense blocks in training without concatenations:
+# one buffer per block, the site formed again wherever it is needed), an eleventh table, bound last
+DENSETRAIN_SIGNATURES, _DENSETRAIN_STRUCTS, _DENSETRAIN_CONSTANTS = _header.read(
+    os.path.join(_HERE, "..", "include", "alignq_dense_train.h"))
+
 
 class SiteBnArgs(ctypes.Structure):
     """include/alignq.h: alignq_site_bn_args (one site of alignq_site_partials_bn_twin; the arguments of alignq_site_partials_bn)"""
@@ -115,7 +120,8 @@ def load():
                                   ("DIGIT_SIGNATURES", "alignq_digit.h", "digit_eval_kernels.hip"),
                                   ("K3IMAGE_SIGNATURES", "alignq_k3image.h", "k3image_kernels.hip"),
                                   ("BNQANY_SIGNATURES", "alignq_bnq_any.h", "bnq_any_kernels.hip"),
-                                  ("BNQPOOL_SIGNATURES", "alignq_bnq_pool.h", "bnq_pool_kernels.hip")):
+                                  ("BNQPOOL_SIGNATURES", "alignq_bnq_pool.h", "bnq_pool_kernels.hip"),
+                                  ("DENSETRAIN_SIGNATURES", "alignq_dense_train.h", "dense_train_kernels.hip")):
         for name, (res, args) in globals()[table].items():
             try:
                 fn = getattr(lib, name)

@@ -69,6 +69,8 @@ inline int parts_for(int64_t P, int C, int64_t* per_out, int slot_pixels = kSlot
 
 // ---- per-channel sums over a workgroup's pixels -----------------------------------------------------------------------------------
 // MODE 0: {sum z, sum z^2};  MODE 1: {sum dx, sum dx * zhat}.  part: [gridDim.x][C][2] doubles.  blockDim.x = the Geo's NT.
+// ldq: float4 between two pixels of z (C / 4 for a dense tensor; dense_train_kernels.hip reads the first C channels of a wider
+// buffer: same partition, same order, same bits).  g and the mask are dense.
 template <int Q>
 __device__ __forceinline__ void slot_reduce(double* __restrict__ sm, const double (&s)[Q][4], int C, int L, int slots, int which,
                                             double* __restrict__ part) {
@@ -91,8 +93,8 @@ __device__ __forceinline__ void slot_reduce(double* __restrict__ sm, const doubl
 template <int MODE, int Q>
 __global__ __launch_bounds__(kMaxNT) void any_sums_kernel(const float* __restrict__ z, const float* __restrict__ g,
                                                           const unsigned long long* __restrict__ mask, const float* __restrict__ ab,
-                                                          const float* __restrict__ save, int64_t P, int C, int L, int slots,
-                                                          int64_t per, float r, double* __restrict__ part) {
+                                                          const float* __restrict__ save, int64_t P, int C, int64_t ldq, int L,
+                                                          int slots, int64_t per, float r, double* __restrict__ part) {
   constexpr int U = (MODE == 0 ? 8 : 4) / Q;                 // float4 per thread, array and quad in flight
   __shared__ double sm[kMaxNT * Q * 4];
   const int tid = threadIdx.x, C4 = C >> 2;
@@ -124,11 +126,11 @@ __global__ __launch_bounds__(kMaxNT) void any_sums_kernel(const float* __restric
 #pragma unroll
       for (int u = 0; u < U; u++) {                          // clamped address, masked below
         const int64_t px = base + (int64_t)u * slots;
-        const int64_t row = (px < p1 ? px : p1 - 1) * C4;
+        const int64_t pc = px < p1 ? px : p1 - 1;
 #pragma unroll
         for (int q = 0; q < Q; q++) {
-          const int64_t i = row + qd[q];
-          zv[u][q] = ld4(z + 4 * i);
+          const int64_t i = pc * C4 + qd[q];
+          zv[u][q] = ld4(z + 4 * (pc * ldq + qd[q]));
           if (MODE == 1) {
             gv[u][q] = ld4(g + 4 * i);
             if (mask) mask_bits4(mask, i, mk[u][q]);

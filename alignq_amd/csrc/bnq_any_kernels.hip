@@ -196,9 +196,9 @@ template <int MODE>
 inline void launch_sums(const Geo& ge, int np, hipStream_t st, const float* z, const float* g, const unsigned long long* mask,
                         const float* ab, const float* save, int64_t P, int C, int64_t per, float r, double* part) {
   if (ge.Q == 2)
-    hipLaunchKernelGGL((any_sums_kernel<MODE, 2>), dim3(np), dim3(ge.NT), 0, st, z, g, mask, ab, save, P, C, ge.L, ge.slots, per, r, part);
+    hipLaunchKernelGGL((any_sums_kernel<MODE, 2>), dim3(np), dim3(ge.NT), 0, st, z, g, mask, ab, save, P, C, (int64_t)(C >> 2), ge.L, ge.slots, per, r, part);
   else
-    hipLaunchKernelGGL((any_sums_kernel<MODE, 1>), dim3(np), dim3(ge.NT), 0, st, z, g, mask, ab, save, P, C, ge.L, ge.slots, per, r, part);
+    hipLaunchKernelGGL((any_sums_kernel<MODE, 1>), dim3(np), dim3(ge.NT), 0, st, z, g, mask, ab, save, P, C, (int64_t)(C >> 2), ge.L, ge.slots, per, r, part);
 }
 
 }  // namespace

@@ -271,8 +271,8 @@ int alignq_bnq_pool_fwd(const float* z, int64_t B, int H, int W, int C, const fl
   int64_t per;
   const int np = parts_for(s.P, C, &per);
   hipLaunchKernelGGL((any_sums_kernel<0, 1>), dim3(np), dim3(ge.NT), 0, st, z, (const float*)nullptr,
-                     (const unsigned long long*)nullptr, (const float*)nullptr, (const float*)nullptr, s.P, C, ge.L, ge.slots, per,
-                     act_range, part);
+                     (const unsigned long long*)nullptr, (const float*)nullptr, (const float*)nullptr, s.P, C, (int64_t)(C >> 2), ge.L,
+                     ge.slots, per, act_range, part);
   hipLaunchKernelGGL(any_finalize_fwd_kernel, dim3((C + kFinT - 1) / kFinT), dim3(kFinT), 0, st, (const double*)part, np, s.P, C, gamma,
                      beta, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, bn_eps, ab, save);
   const int64_t nvec = s.PP * (C >> 2);

@@ -64,4 +64,20 @@ __device__ __forceinline__ float4 site_q(const float4 v, const float* ab, int C,
   return o;
 }
 
+// The TRAINING statement of the same site (include/alignq_bnq_any.h, "forward"): x = fma(a, z, b), one rounding, then the quantiser.
+// a and b come from the batch's statistics (the [2][C] `ab` alignq_bnq_any_fwd writes), so there is no k == 32 form.
+template <int FORMULA, bool BOUNDED>
+__device__ __forceinline__ float4 site_q_fma(const float4 v, const float* ab, int C, int cq, int k, const Levels& nlev, float r,
+                                             const NerfTab tab) {
+  const float4 a4 = *reinterpret_cast<const float4*>(ab + 4 * cq);
+  const float4 b4 = *reinterpret_cast<const float4*>(ab + C + 4 * cq);
+  float t, bin;
+  float4 o;
+  o.x = act_quant1<FORMULA, BOUNDED>(__fmaf_rn(a4.x, v.x, b4.x), k, nlev, r, &t, &bin, tab);
+  o.y = act_quant1<FORMULA, BOUNDED>(__fmaf_rn(a4.y, v.y, b4.y), k, nlev, r, &t, &bin, tab);
+  o.z = act_quant1<FORMULA, BOUNDED>(__fmaf_rn(a4.z, v.z, b4.z), k, nlev, r, &t, &bin, tab);
+  o.w = act_quant1<FORMULA, BOUNDED>(__fmaf_rn(a4.w, v.w, b4.w), k, nlev, r, &t, &bin, tab);
+  return o;
+}
+
 }  // namespace alignq_evalsite

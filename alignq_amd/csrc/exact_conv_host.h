@@ -28,4 +28,26 @@ inline int n_tile_width(int N) {
 // the write-through window (store_forms.h): outputs of 1 MiB to 64 MiB are stored through to memory
 inline bool write_through(int64_t out_bytes) { return out_bytes >= ((int64_t)1 << 20) && out_bytes <= ((int64_t)64 << 20); }
 
+// The 3x3 filter gradient's launch geometry (k3conv_kernels.hip; dense_train_kernels.hip runs the same slabs): a step is one
+// 4 x 8 pixel tile, the four waves lie along CIN (64 x 16) or along COUT (16 x 64), and split-K runs over slabs of spatial tiles:
+// enough workgroups for the chip, at least two steps per slab, no empty slab.
+constexpr int kK3WgradTileH = 4, kK3WgradTileW = 8;
+struct K3WgradGeom { int cb, ob, th, tw, s_tiles, c_tiles, o_tiles, per, splits; };
+inline K3WgradGeom k3_wgrad_geometry(int B, int H, int W, int CIN, int COUT) {
+  K3WgradGeom g{};
+  g.cb = CIN >= COUT ? 64 : 16; g.ob = CIN >= COUT ? 16 : 64;
+  g.th = (H + kK3WgradTileH - 1) / kK3WgradTileH; g.tw = (W + kK3WgradTileW - 1) / kK3WgradTileW;
+  g.s_tiles = B * g.th * g.tw;
+  g.c_tiles = (CIN + g.cb - 1) / g.cb; g.o_tiles = (COUT + g.ob - 1) / g.ob;
+  const int tiles = g.c_tiles * g.o_tiles;
+  int s = (512 + tiles - 1) / tiles;
+  const int max_s = (g.s_tiles + 1) / 2;
+  if (s > max_s) s = max_s;
+  if (s > 1024) s = 1024;
+  if (s < 1) s = 1;
+  g.per = (g.s_tiles + s - 1) / s;
+  g.splits = (g.s_tiles + g.per - 1) / g.per;
+  return g;
+}
+
 }  // namespace alignq_xmma

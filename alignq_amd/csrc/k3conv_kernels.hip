@@ -350,25 +350,8 @@ int launch_gemm(const float* a, const void* w, float* out, int B, int H, int W, 
   return e == hipSuccess ? 0 : (int)e;
 }
 
-// split-K over slabs of spatial tiles: enough workgroups for the chip, at least two steps per slab, no empty slab
-struct WGeom { int form, th, tw, s_tiles, c_tiles, o_tiles, per, splits; };
-inline WGeom wgrad_geometry(int B, int H, int W, int CIN, int COUT) {
-  WGeom g{};
-  g.form = wgrad_form(CIN, COUT);
-  const int cb = g.form == ALIGNQ_K3_FORM_W64X16 ? 64 : 16, ob = g.form == ALIGNQ_K3_FORM_W64X16 ? 16 : 64;
-  g.th = (H + WTH - 1) / WTH; g.tw = (W + WTW - 1) / WTW;
-  g.s_tiles = B * g.th * g.tw;
-  g.c_tiles = (CIN + cb - 1) / cb; g.o_tiles = (COUT + ob - 1) / ob;
-  const int tiles = g.c_tiles * g.o_tiles;
-  int s = (512 + tiles - 1) / tiles;
-  const int max_s = (g.s_tiles + 1) / 2;
-  if (s > max_s) s = max_s;
-  if (s > 1024) s = 1024;
-  if (s < 1) s = 1;
-  g.per = (g.s_tiles + s - 1) / s;
-  g.splits = (g.s_tiles + g.per - 1) / g.per;
-  return g;
-}
+// split-K over slabs of spatial tiles: k3_wgrad_geometry (exact_conv_host.h), whose cb x ob is wgrad_form's
+static_assert(WTH == kK3WgradTileH && WTW == kK3WgradTileW, "the geometry's tile is the kernel's");
 
 }  // namespace
 
@@ -399,7 +382,7 @@ int alignq_k3conv_dgrad(const float* dy, const void* w_bins, float* dx, int B, i
 
 size_t alignq_k3conv_wgrad_ws_bytes(int B, int H, int W, int CIN, int COUT) {
   if (!shape_ok(B, H, W, CIN, COUT)) return 0;
-  const WGeom g = wgrad_geometry(B, H, W, CIN, COUT);
+  const K3WgradGeom g = k3_wgrad_geometry(B, H, W, CIN, COUT);
   return (size_t)g.splits * (size_t)COUT * 9 * CIN * sizeof(float);
 }
 
@@ -408,7 +391,7 @@ int alignq_k3conv_wgrad(const float* x, const float* dy, float* dw, void* ws, in
   if (!x || !dy || !ws || (!dw && !n_slabs_out) || !aligned16(x) || !aligned16(dy) || !aligned16(ws) || !aligned16(dw))
     return ALIGNQ_EINVAL;
   if (!shape_ok(B, H, W, CIN, COUT)) return ALIGNQ_EUNSUPPORTED;
-  const WGeom g = wgrad_geometry(B, H, W, CIN, COUT);
+  const K3WgradGeom g = k3_wgrad_geometry(B, H, W, CIN, COUT);
   K3W a{};
   a.x = x; a.dy = dy; a.slabs = (float*)ws;
   a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
@@ -416,7 +399,7 @@ int alignq_k3conv_wgrad(const float* x, const float* dy, float* dw, void* ws, in
   a.c_tiles = g.c_tiles; a.o_tiles = g.o_tiles;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(g.c_tiles * g.o_tiles * g.splits), blk(256);
-  if (g.form == ALIGNQ_K3_FORM_W64X16) hipLaunchKernelGGL((k3_wgrad_kernel<64, 16>), grid, blk, 0, st, a);
+  if (g.cb == 64) hipLaunchKernelGGL((k3_wgrad_kernel<64, 16>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((k3_wgrad_kernel<16, 64>), grid, blk, 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;

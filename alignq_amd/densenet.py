@@ -16,7 +16,10 @@ the two transitions on csrc/pointwise_kernels.hip; the 3 -> 24 stem, batch-norm,
 rocBLAS through PyTorch-ROCm.  With use_hip_convs(model, stem=True) the stem runs on csrc/k3image_kernels.hip
 (include/alignq_k3image.h) as well, and every Conv2d_Q of the model has arithmetic this repository defines.  The sites run as the
 composition, or, with use_hip_convs(model, train_sites=True), folded in training: batch-norm, quantiser and ReLU as three launches each way
-on csrc/bnq_any_kernels.hip (include/alignq_bnq_any.h) at every width.  Training is eager iterations (alignq_amd.optimizer.SGD).
+on csrc/bnq_any_kernels.hip (include/alignq_bnq_any.h) at every width.  With use_hip_convs(model, dense_train=True) a training
+forward also runs every dense block as ONE autograd node on ONE buffer (fused.DenseBlockFn, csrc/dense_train_kernels.hip,
+include/alignq_dense_train.h): nothing is concatenated, and neither a copy of a layer's input nor its quantised activation nor a mask is
+kept for the backward; the bits are those of train_sites=True.  Training is eager iterations (alignq_amd.optimizer.SGD).
 
 Evaluation (eval_step.EvalStep) with use_hip_convs(model, dense_eval=True): DenseNet._forward_eval keeps ONE buffer per dense block;
 a dense layer is one alignq_dense_layer_eval_fwd launch (include/alignq_dense.h: the site applied while the convolution stages its
@@ -97,6 +100,7 @@ class Transition(nn.Module):
 class DenseNet(nn.Module):
     fuse_dense_eval = False           # kernel-path flag, off unless set (alignq_amd.paths; INTEGRATION.md, "Kernel-path flags")
     fuse_train_sites = False          # likewise
+    fuse_dense_train = False          # likewise
 
     def __init__(self, wbit, abit, stage, depth=40, block=DenseBasicBlock, dropRate=0, num_classes=10, growthRate=12,
                  compressionRate=2, filters=None, indexes=None):
@@ -149,12 +153,21 @@ class DenseNet(nn.Module):
     def forward(self, x):
         if self.fuse_dense_eval and fused.eval_active():
             return self._forward_eval(x)
-        x = self.dense1(self.conv1(x))
-        x = self.dense2(self.trans1(x))
-        x = self.dense3(self.trans2(x))
+        x = self._dense(self.dense1, self.conv1(x))
+        x = self._dense(self.dense2, self.trans1(x))
+        x = self._dense(self.dense3, self.trans2(x))
         x = self.avgpool(_site(self, self.bn, self.act_q0, x))
         return self.fc(x.reshape(x.size(0), -1))
 
+    def _dense(self, dense, x):
+        """One dense block: with `fuse_dense_train` on, a training forward runs it as one node on one buffer (fused.dense_block_train);
+        where that does not apply (dropout, a batch-norm without tracked statistics, another quantiser, an unsupported shape), and
+        always with the flag off, it is the modules."""
+        if self.fuse_dense_train and self.training and not fused.eval_active():
+            out = fused.dense_block_train(dense, x)
+            if out is not None:
+                return out
+        return dense(x)
 
     # ---- evaluation without concatenations (inside fused.eval_scope: eval_step.EvalStep) ----
     def _forward_eval(self, x):
@@ -221,7 +234,7 @@ def densenet_40_quant(bitW, abitW, stage, pretrained=False, **kwargs):
     return DenseNet(wbit=bitW, abit=abitW, stage=stage, depth=40, block=DenseBasicBlock, compressionRate=1, **kwargs)
 
 
-def use_hip_convs(model, dense_eval=False, stem=False, train_sites=False):
+def use_hip_convs(model, dense_eval=False, stem=False, train_sites=False, dense_train=False):
     """Channels-last parameters plus `use_qconv`, `use_qconv_pw` (the transitions) and `use_qconv_k3` (the dense layers): with
     channels-last inputs every dense layer then runs on alignq_k3conv_* and both transitions on alignq_pwconv_*; the concatenations keep
     the layout, so no dense layer falls back to MIOpen.  Values, parameter names and state_dict are unchanged.
@@ -230,13 +243,18 @@ def use_hip_convs(model, dense_eval=False, stem=False, train_sites=False):
     stem=True also sets `use_qconv_k3_image`: the 3 -> 24 stem then runs on alignq_k3image_*, and inside _forward_eval it writes into
     the first block's buffer by one launch.  Without it every launch is what it was.
     train_sites=True also sets `fuse_train_sites`: in training forwards every bn -> act_q0 -> ReLU site (dense layers, transitions, head)
-    then runs folded on alignq_bnq_any_* (include/alignq_bnq_any.h).  Without it every launch is what it was."""
+    then runs folded on alignq_bnq_any_* (include/alignq_bnq_any.h).  Without it every launch is what it was.
+    dense_train=True implies train_sites and also sets `fuse_dense_train`: in training forwards every dense block then runs as one
+    fused.DenseBlockFn node on alignq_dense_train_* (include/alignq_dense_train.h), with the bits of train_sites=True.  Without it every
+    launch is what it was."""
     model = model.to(memory_format=torch.channels_last)
     paths.apply(model, use_qconv=True, use_qconv_pw=True, use_qconv_k3=True)
     if stem:
         paths.apply(model, use_qconv_k3_image=True)
     if dense_eval:
         paths.apply(model, fuse_dense_eval=True)
-    if train_sites:
+    if train_sites or dense_train:
         paths.apply(model, fuse_train_sites=True)
+    if dense_train:
+        paths.apply(model, fuse_dense_train=True)
     return model

@@ -1008,6 +1008,126 @@ def bn_act_any(bn, act, z, clamp):
                               act.a_bit, config.args.act_range, formula, clamp)
 
 
+# ---- a whole dense block in training without concatenations (include/alignq_dense_train.h, csrc/dense_train_kernels.hip) ----
+# densenet.py:31-41 for every layer of a block: ONE buffer [B][H][W][C_end] and one gradient buffer; a layer reads the buffer's first
+# CIN channels and writes its C_out behind them.  Saved for the backward: the buffer and, per layer, ab / save ([2][CIN] each) - no copy
+# of the input, no quantised activation, no mask.  Every launch has the bits of the BNQuantAnyFn / QConvK3Fn launch it replaces, and
+# walking the layers last to first makes each update of G the two-term add autograd performs for `cat` plus the site.
+_DB = 7          # tensors per layer: bn.weight, bn.bias, running_mean, running_var, num_batches_tracked, W_q, its bf16 bins
+
+
+class DenseBlockFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cfg, *tensors):
+        """cfg: (k, act_range, formula, w_bit, ((momentum, bn_eps) per layer)); tensors: _DB per layer.  The weight quantiser stays
+        outside: W_q is an input and its gradient an output."""
+        k, act_range, formula, w_bit, bn_cfg = cfg
+        x = L.dense_f32(x, "dense block input")
+        B, C0, H, W = x.shape
+        P, n = B * H * W, len(tensors) // _DB
+        lib, dev, st = L.load(), x.device, L.stream_ptr()
+        c_end = C0 + sum(int(tensors[_DB * i + 5].shape[0]) for i in range(n))
+        buf = torch.empty((B, c_end, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        buf[:, :C0].copy_(x)
+        base, cin, kept = buf.data_ptr(), C0, []
+        for i in range(n):
+            gamma, beta, rmean, rvar, nbt, wq, bins = tensors[_DB * i:_DB * i + _DB]
+            cout = int(wq.shape[0])
+            ab = torch.empty(2, cin, dtype=torch.float32, device=dev)
+            save = torch.empty(2, cin, dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.alignq_dense_train_site_ws_bytes(P, cin), dtype=torch.uint8, device=dev)
+            L.check(lib.alignq_dense_train_stats(base, c_end, P, cin, L.ptr(gamma), L.ptr(beta), L.ptr(rmean), L.ptr(rvar), L.ptr(nbt),
+                                                 float(bn_cfg[i][0]), float(bn_cfg[i][1]), L.ptr(ab), L.ptr(save), L.ptr(ws), st),
+                    "alignq_dense_train_stats")
+            L.check(lib.alignq_dense_train_layer_fwd(base, c_end, base + 4 * cin, c_end, L.ptr(ab), L.ptr(bins), B, H, W, cin, cout,
+                                                     int(w_bit), int(k), float(act_range), int(formula), st),
+                    "alignq_dense_train_layer_fwd")
+            kept += [ab, save, wq, bins]
+            cin += cout
+        ctx.save_for_backward(buf, *kept)
+        ctx.cfg = (int(k), float(act_range), int(formula), int(w_bit), C0,
+                   tuple((tensors[_DB * i] is not None, tensors[_DB * i + 1] is not None) for i in range(n)))
+        return buf
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        buf, *kept = ctx.saved_tensors
+        k, act_range, formula, w_bit, C0, affine = ctx.cfg
+        B, c_end, H, W = buf.shape
+        P, n = B * H * W, len(affine)
+        lib, dev, st, cl = L.load(), buf.device, L.stream_ptr(), torch.channels_last
+        G = torch.empty_like(buf)          # (a copy: it is updated in place)
+        G.copy_(g)
+        z, Gp = buf.data_ptr(), G.data_ptr()
+        couts = [int(kept[4 * i + 2].shape[0]) for i in range(n)]
+        grads = [None] * (_DB * n)
+        for i in reversed(range(n)):
+            ab, save, wq, bins = kept[4 * i:4 * i + 4]
+            cin, cout = C0 + sum(couts[:i]), couts[i]
+            dy = Gp + 4 * cin              # complete: every later layer has added its share
+            gy = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev, memory_format=cl)
+            L.check(lib.alignq_dense_train_dgrad(dy, c_end, L.ptr(bins), L.ptr(gy), B, H, W, cin, cout, w_bit, st),
+                    "alignq_dense_train_dgrad")
+            if ctx.needs_input_grad[2 + _DB * i + 5]:
+                dw = torch.empty_like(wq)
+                ws = ops._ws(lib.alignq_dense_train_wgrad_ws_bytes(B, H, W, cin, cout), dev)
+                ops._filter_grad(ws, dw, cout * 9 * cin, lambda dwp, nsp: L.check(lib.alignq_dense_train_wgrad(
+                    z, c_end, L.ptr(ab), dy, c_end, dwp, L.ptr(ws), B, H, W, cin, cout, k, act_range, formula, nsp, st),
+                    "alignq_dense_train_wgrad"))
+                grads[_DB * i + 5] = dw
+            dgamma = torch.empty(cin, dtype=torch.float32, device=dev) if affine[i][0] else None
+            dbeta = torch.empty(cin, dtype=torch.float32, device=dev) if affine[i][1] else None
+            ws = torch.empty(lib.alignq_dense_train_site_ws_bytes(P, cin), dtype=torch.uint8, device=dev)
+            L.check(lib.alignq_dense_train_site_bwd(L.ptr(gy), z, c_end, L.ptr(ab), L.ptr(save), Gp, c_end, P, cin, k, act_range,
+                                                    formula, L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), st),
+                    "alignq_dense_train_site_bwd")
+            grads[_DB * i], grads[_DB * i + 1] = dgamma, dbeta
+        return (G[:, :C0].contiguous(memory_format=cl), None, *grads)
+
+
+def dense_block_train(dense, x):
+    """dense(x) for a Sequential of densenet.DenseBasicBlock in training by one DenseBlockFn node, or None where it does not apply (the
+    caller runs the modules): no dropout; every layer a training nn.BatchNorm2d with tracked statistics and a momentum, a plain
+    quantiser with a_bit <= 16 and a 3x3 Conv2d_Q on `use_qconv` / `use_qconv_k3` whose shape alignq_dense_train_supported accepts in
+    the block's buffer; x a channels-last fp32 CUDA tensor of the first layer's width.  The weight quantisers run here, in layer order."""
+    from . import config, ops
+    if not (len(dense) and _nhwc_f32(x) and x.shape[1] == dense[0].bn1.num_features and x.numel() >= 2 * x.shape[1]):
+        return None
+    B, cin, H, W = x.shape
+    c_end = cin + sum(layer.conv1.out_channels for layer in dense)
+    lib, act0 = L.load(), dense[0].act_q0
+    k, formula = int(getattr(act0, "a_bit", 32)), getattr(act0, "_formula", None)
+    w_bit = int(getattr(dense[0].conv1.quantize_fn, "w_bit", 32))
+    if not (1 <= k <= 16 and formula in (L.FORMULA_ADMM, L.FORMULA_CDF) and 1 <= w_bit <= 8):
+        return None
+    for layer in dense:
+        bn, act, conv = layer.bn1, layer.act_q0, layer.conv1
+        if layer.dropRate > 0 or not (getattr(conv, "use_qconv", False) and getattr(conv, "use_qconv_k3", False)):
+            return None
+        if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.track_running_stats and bn.momentum is not None
+                and bn.running_mean is not None and bn.num_features == cin):
+            return None
+        if hasattr(act, "opt") or int(getattr(act, "a_bit", 32)) != k or getattr(act, "_formula", None) != formula:
+            return None
+        if int(getattr(conv.quantize_fn, "w_bit", 32)) != w_bit or not ops.qconv_k3_shape_supported(
+                (B, cin, H, W), conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, w_bit):
+            return None
+        if lib.alignq_dense_train_supported(B, H, W, cin, conv.out_channels, c_end) != 1:
+            return None
+        cin += conv.out_channels
+    tensors = []
+    for layer in dense:
+        bn, q = layer.bn1, layer.conv1.quantize_fn
+        wq = q(layer.conv1.weight)
+        bins = q.filter_of(wq).bins
+        if bins is None:
+            bins = ops.pack_filter_bins([wq.detach()], w_bit)[0]
+        tensors += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, wq, bins[0]]
+    cfg = (k, config.args.act_range, formula, w_bit, tuple((m.bn1.momentum, m.bn1.eps) for m in dense))
+    return DenseBlockFn.apply(x, cfg, *tensors)
+
+
 # ---- the fold with a ReLU and a 2 x 2 max-pool behind it (include/alignq_bnq_pool.h, csrc/bnq_pool_kernels.hip) ----
 # `MaxPool2d(2)(ReLU(act_q(bn(z))))` of dann_digit/model/dann.py's `feature`: three launches each way; the backward's statistics read the
 # pooled elements only, and neither the un-pooled output nor the un-pooled gradient is ever written.

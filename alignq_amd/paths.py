@@ -7,7 +7,8 @@ one module works as before."""
 from __future__ import annotations
 
 FLAGS = ("use_qconv", "use_qconv_pw", "emit_bn_stats", "fuse_bn", "fuse_relu", "pack_bins", "_wq_stage", "use_qconv_k3",
-         "use_qconv_k5", "use_qconv_k3_image", "fuse_digit_eval", "fuse_train_sites", "fuse_dense_eval")
+         "use_qconv_k5", "use_qconv_k3_image", "fuse_digit_eval", "fuse_train_sites", "fuse_dense_train",
+         "fuse_dense_eval")
 _ABSENT = object()
 
 
